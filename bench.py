@@ -16,6 +16,13 @@ under 1 % (``--batch 384`` for the last bit).  The eager engine defaults to 128 
 16 the step is dominated by fixed-cost launches and, under DDP, SyncBN exchanges; ``--batch 16``
 reproduces MyConfig's per-process batch.
 
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print the JSON
+line.  ``--full`` adds the measurements that take runs of their own after the timed region: the validation
+Dice of this short run and, on a multi-rank job, the communication evidence pass (``comm``).
+``--dump-outputs DIR`` writes what the last timed step returned and left behind (its loss, the trained
+model's state) as ``DIR/<name>.npy``; the inputs depend only on the arguments, so two builds can be
+compared output for output.
+
 ``--impl fused`` (default) runs the MI355X-native engine (HIP kernels + hipGraph); ``--impl eager``
 runs the same step with stock PyTorch-ROCm (MIOpen convs, torch DDP/SyncBN) = the in-house
 "reference speed" of BASELINE.md.
@@ -66,8 +73,14 @@ def parse_args(argv=None):
     p.add_argument('--lr', type=float, default=1e-3, help='Adam lr per GPU (reference: 0.1 * base_lr * gpu_num)')
     p.add_argument('--seed', type=int, default=1, help='trainer random_seed (model init, data order; MyConfig: 1)')
     p.add_argument('--comm-steps', type=int, default=3,
-                   help='multi-GPU evidence pass after the timed region (0 = off): per-bucket RCCL timings, SyncBN '
-                        'exchange count/time, and the step time with every collective knocked out')
+                   help='multi-GPU evidence pass after the timed region, run with --full (0 = off): per-bucket RCCL '
+                        'timings, SyncBN exchange count/time, and the step time with every collective knocked out')
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps also run what the headline figure does not need: the validation Dice '
+                        'of this short run and, on a multi-rank job, the communication evidence pass')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps write what the last timed step returned and left behind as '
+                        'DIR/<name>.npy (float32): loss.npy and model_state.npy (see dump_outputs)')
     a = p.parse_args(argv)
     if a.batch is None:
         a.batch = 320 if a.impl == 'fused' and a.model == 'ducknet' and a.base_channel == 17 else 128
@@ -205,6 +218,28 @@ def comm_evidence(step, args, dist, step_ms, device):
     return out
 
 
+DUMP_STATE_MAX_ELEMS = 12 * 2 ** 20   # model_state.npy holds at most 48 MiB of float32
+
+
+def dump_outputs(step, loss, out_dir):
+    """What a caller of the timed step holds after the last timed step, as float32 ``.npy`` files:
+    ``loss.npy`` -- the loss that step returned; ``model_state.npy`` -- the trained model's state after it
+    (every floating-point parameter and buffer in ``state_dict`` order, flattened and concatenated; a model
+    with more than ``DUMP_STATE_MAX_ELEMS`` elements is reduced to that many at fixed positions drawn with
+    seed 0, so two builds dump the same positions)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'loss.npy'), loss.detach().float().cpu().numpy().reshape(-1))
+    model = step.trainer.model if hasattr(step, 'trainer') else getattr(step, 'model_ref', None) or step.model
+    with torch.no_grad():
+        state = torch.cat([v.detach().float().flatten().cpu() for v in model.state_dict().values()
+                           if v.is_floating_point()]).numpy()
+    if state.size > DUMP_STATE_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(0).integers(0, state.size, DUMP_STATE_MAX_ELEMS))
+        state = state[idx]
+    np.save(os.path.join(out_dir, 'model_state.npy'), np.ascontiguousarray(state, dtype=np.float32))
+
+
 def model_label(args):
     if args.model == 'ducknet':
         name = f'DUCKNet-{args.base_channel}'
@@ -307,6 +342,11 @@ def main(argv=None):
         if not cuda:
             cfg.base_workers = 0   # CPU rehearsal: batches built in-process
         step = TrainerStep(cfg, fixed=args.data == 'fixed')
+        tf = getattr(getattr(step.loader, 'dataset', None), 'transform', None)
+        if not cuda and hasattr(tf, 'seed'):
+            # CPU rehearsal: the in-process host loader's augmentation draws from an unseeded stream (the
+            # device loader seeds its own): seed it, so that equal arguments give equal batches here too
+            tf.seed(args.seed + rank)
     else:
         from medical_segmentation_pytorch_amd.runtime.bench_step import build_bench_step
         feed = make_feed(args, device, seed=1000 + rank) if args.data == 'augment' else None
@@ -336,8 +376,9 @@ def main(argv=None):
         dist.barrier()
     sync()
     t0 = time.perf_counter()
+    last_loss = None
     for _ in range(args.steps):
-        step()
+        last_loss = step()
     sync()
     if dist is not None:
         dist.barrier()
@@ -351,8 +392,13 @@ def main(argv=None):
     ms = elapsed / args.steps * 1e3
     global_batch = args.batch * world
     value = global_batch * args.steps / elapsed
+    if args.dump_outputs and rank == 0 and last_loss is not None:
+        # (every rank holds the same weights after the step's gradient all-reduce: rank 0 writes)
+        dump_outputs(step, last_loss, args.dump_outputs)
     dice = fg_dice = None
-    if args.val_images > 0 and hasattr(step, 'validate') and args.model in ('ducknet', 'unet'):
+    if not args.full:
+        pass   # a plain run stops at the headline figure
+    elif args.val_images > 0 and hasattr(step, 'validate') and args.model in ('ducknet', 'unet'):
         # the trainer's own validation (EMA model = live weights with use_ema=False, MyConfig) after this
         # run's W+K steps; every rank takes part (the confusion matrix is all-reduced)
         dice, fg_dice = step.validate()
@@ -363,7 +409,7 @@ def main(argv=None):
     # config (profiles/eager_reference_speed.json), times the GPU count (weak scaling; generous to the
     # eager side, whose DDP+SyncBN would scale sub-linearly).
     comm = None
-    if dist is not None and args.comm_steps > 0 and impl == 'fused' and not use_graph:
+    if args.full and dist is not None and args.comm_steps > 0 and impl == 'fused' and not use_graph:
         comm = comm_evidence(step, args, dist, ms, device)
     baseline = None
     here = os.path.dirname(os.path.abspath(__file__))

@@ -263,7 +263,7 @@ def test_bench_self_launches_ranks(tmp_path):
     env.update(OMP_NUM_THREADS='2', BENCH_SAVE_DIR=str(tmp_path / 'save'))
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
            '--batch', '2', '--size', '64', '--model', 'unet', '--base-channel', '8', '--train-images', '8',
-           '--val-images', '2', '--comm-steps', '1']
+           '--val-images', '2', '--comm-steps', '1', '--full']
     out = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
@@ -271,6 +271,43 @@ def test_bench_self_launches_ranks(tmp_path):
     d = json.loads(lines[0])
     assert d['n_gpus'] == 2 and d['config']['parallelism'] == 'dp2' and d['config']['global_batch'] == 4
     assert d['comm']['world_size'] == 2 and d['value'] > 0
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain ``bench.py --gpus 1`` run stops at the headline figure (no validation Dice, no evidence pass;
+    ``--steps`` is the number of timed steps, ``ms_per_step`` their mean) and ``--dump-outputs DIR`` writes
+    the last timed step's loss and the trained model's state as float32 ``.npy`` files that a second run with
+    the same arguments reproduces."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('LOCAL_RANK', 'RANK', 'WORLD_SIZE', 'MASTER_PORT')}
+    env.update(OMP_NUM_THREADS='2')
+    dumps = []
+    for tag in ('a', 'b'):
+        env['BENCH_SAVE_DIR'] = str(tmp_path / f'save_{tag}')
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+               '--batch', '2', '--size', '64', '--model', 'unet', '--base-channel', '8', '--train-images', '8',
+               '--val-images', '2', '--dump-outputs', str(tmp_path / tag)]
+        out = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, out.stdout
+        d = json.loads(lines[0])
+        assert d['steps'] == 2 and d['ms_per_step'] > 0 and d['unit'] == 'images/sec' and d['higher_is_better']
+        assert abs(d['value'] - 2 * 1e3 / d['ms_per_step']) <= 0.01 * d['value']   # batch 2 per step
+        assert d['val_dice'] is None and 'comm' not in d
+        assert sorted(os.listdir(tmp_path / tag)) == ['loss.npy', 'model_state.npy']
+        dumps.append({n: np.load(tmp_path / tag / f'{n}.npy') for n in ('loss', 'model_state')})
+    a, b = dumps
+    assert a['loss'].dtype == np.float32 and a['loss'].shape == (1,) and np.isfinite(a['loss']).all()
+    assert a['model_state'].dtype == np.float32 and a['model_state'].ndim == 1 and a['model_state'].size > 1000
+    assert a['model_state'].nbytes + a['loss'].nbytes <= 64 * 2 ** 20 and np.isfinite(a['model_state']).all()
+    # the same arguments give the same inputs, so the CPU engine's two runs agree to float32 rounding
+    assert np.allclose(a['loss'], b['loss'], rtol=1e-4, atol=1e-6)
+    assert np.allclose(a['model_state'], b['model_state'], rtol=1e-4, atol=1e-5)
 
 
 def test_bench_refuses_mismatched_world(tmp_path):

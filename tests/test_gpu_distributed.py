@@ -134,7 +134,7 @@ def test_bench_ddp_path_two_ranks(gpu, tmp_path):
     env = dict(os.environ, BENCH_DIST_BACKEND='gloo', BENCH_SAME_DEVICE='1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2', '--master-addr',
            '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3',
-           '--warmup', '2', '--batch', '2', '--size', '64', '--train-images', '8', '--val-images', '4']
+           '--warmup', '2', '--batch', '2', '--size', '64', '--train-images', '8', '--val-images', '4', '--full']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -158,7 +158,7 @@ def test_bench_rccl_path_world1(gpu, tmp_path):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=1', '--master-addr',
            '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--ddp',
            '--steps', '3', '--warmup', '2', '--batch', '4', '--size', '64', '--train-images', '8',
-           '--val-images', '4', '--graph-ddp', 'off']
+           '--val-images', '4', '--graph-ddp', 'off', '--full']
     r = subprocess.run(cmd, env=dict(os.environ), capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     errs = [ln for ln in r.stderr.splitlines() if 'rror' in ln or 'what()' in ln or 'Exception' in ln][:20]
     assert r.returncode == 0, '\n'.join(errs) + '\n...\n' + r.stderr[-2000:]
