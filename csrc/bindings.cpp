@@ -668,6 +668,53 @@ void bce_dice_grad_t(const at::Tensor& x, const at::Tensor& t, const at::Tensor&
 
 int64_t bce_dice_splits_t(int64_t HW) { return bce_dice_splits(HW); }
 
+int64_t region_splits_t(int64_t HW) { return region_splits(HW); }
+
+// shared checks of the two region-loss passes; returns {N, C, HW}
+static std::tuple<int, int, long> region_check(const at::Tensor& logits, const at::Tensor& target,
+                                               const c10::optional<at::Tensor>& weight, const at::Tensor& coef,
+                                               int64_t pix, double gamma, int64_t c0) {
+  CHECK_F32(logits); CHECK_I64(target); CHECK_F32(coef);
+  TORCH_CHECK(logits.dim() == 4, "logits must be NCHW");
+  const int64_t N = logits.size(0), C = logits.size(1), HW = logits.size(2) * logits.size(3);
+  TORCH_CHECK(C >= 2 && C <= region_max_classes(), "region loss: num_class must be in [2, ", region_max_classes(),
+              "] (kMaxC), got ", C);
+  TORCH_CHECK(N >= 1 && N <= 65535 && HW >= 1, "region loss: batch must be in [1, 65535]");
+  TORCH_CHECK(target.numel() == N * HW, "target must be [N, H, W]");
+  TORCH_CHECK(coef.numel() == 2 * N * C + 1, "coef must be [2 N C + 1]");
+  if (weight.has_value()) { CHECK_F32(*weight); TORCH_CHECK(weight->numel() == C, "weight must be [C]"); }
+  TORCH_CHECK(pix >= 0 && pix <= 2, "pix: 0 none, 1 ce, 2 focal");
+  TORCH_CHECK(pix != 2 || gamma >= 1.0, "focal: gamma must be >= 1 (gamma == 0 is ce)");
+  TORCH_CHECK(c0 == 0 || c0 == 1, "c0: first counted class, 0 or 1");
+  return {(int)N, (int)C, (long)HW};
+}
+
+void region_fwd_t(const at::Tensor& logits, const at::Tensor& target, const c10::optional<at::Tensor>& weight,
+                  const at::Tensor& part, const at::Tensor& coef, const at::Tensor& loss, int64_t ignore_index,
+                  int64_t pix, double gamma, double pw, double rw, double a, double b, double smooth, int64_t c0) {
+  const auto [N, C, HW] = region_check(logits, target, weight, coef, pix, gamma, c0);
+  CHECK_F32(part); CHECK_F32(loss);
+  const int splits = region_splits(HW);
+  TORCH_CHECK(part.numel() == (int64_t)N * splits * (2 + 3 * C), "part must be [N, splits, 2 + 3C]");
+  TORCH_CHECK(loss.numel() == 1, "loss must be [1]");
+  auto s = cur_stream();
+  region_stats(f32(logits), target.data_ptr<int64_t>(), f32_opt(weight), f32(part), N, C, HW, (int)ignore_index,
+               (int)pix, (float)gamma, s);
+  region_finalize(f32(part), f32(coef), f32(loss), N, C, splits, (float)pw, (float)rw, (float)a, (float)b,
+                  (float)smooth, (int)c0, s);
+}
+
+void region_grad_t(const at::Tensor& logits, const at::Tensor& target, const c10::optional<at::Tensor>& weight,
+                   const at::Tensor& coef, const at::Tensor& gup, const at::Tensor& grad, int64_t ignore_index,
+                   int64_t pix, double gamma, double pw, double rw, double a, double b, int64_t c0) {
+  const auto [N, C, HW] = region_check(logits, target, weight, coef, pix, gamma, c0);
+  CHECK_F32(gup); CHECK_F32(grad);
+  TORCH_CHECK(gup.numel() == 1 && grad.numel() == logits.numel(), "gup [1], grad like logits");
+  region_grad(f32(logits), target.data_ptr<int64_t>(), f32_opt(weight), f32(coef), f32(gup), f32(grad), N, C, HW,
+              (int)ignore_index, (int)pix, (float)gamma, (float)pw, (float)rw, (float)a, (float)b, (int)c0,
+              cur_stream());
+}
+
 static const float* amp_ptr(const c10::optional<at::Tensor>& amp) {
   if (amp.has_value()) { CHECK_F32(*amp); TORCH_CHECK(amp->numel() >= 4); }
   return f32_opt(amp);
@@ -1206,6 +1253,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("bce_dice_stats", &bce_dice_stats_t);
   m.def("bce_dice_grad", &bce_dice_grad_t);
   m.def("bce_dice_splits", &bce_dice_splits_t);
+  m.def("region_splits", &region_splits_t);
+  m.def("region_max_classes", []() { return region_max_classes(); });
+  m.def("region_fwd", &region_fwd_t);
+  m.def("region_grad", &region_grad_t);
   m.def("adam_step", &adam_step_t, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("hyper"),
         py::arg("adamw"), py::arg("amp") = py::none());
   m.def("sgd_step", &sgd_step_t, py::arg("p"), py::arg("g"), py::arg("buf"), py::arg("hyper"),

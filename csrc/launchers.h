@@ -238,6 +238,18 @@ int bce_dice_splits(long HW);
 void bce_dice_stats(const float* x, const float* t, float* part, int N, long HW, hipStream_t s);
 void bce_dice_grad(const float* x, const float* t, const float* coef, const float* gup, float* grad, int N, long HW,
                    float bw, float dw, hipStream_t s);
+// multi-class pixel (pix: 0 none, 1 CE, 2 focal with gamma >= 1) + region (Tversky a, b, smooth; classes
+// c >= c0 counted) loss, C <= region_max_classes(): part [N][region_splits(HW)][2 + 3C];
+// coef [2NC + 1] = {num, den} per (n, c), then the batch's sum(w); loss [1]; gup device scalar
+int region_max_classes();
+int region_splits(long HW);
+void region_stats(const float* logits, const int64_t* target, const float* weight, float* part, int N, int C,
+                  long HW, int ignore_index, int pix, float gamma, hipStream_t s);
+void region_finalize(const float* part, float* coef, float* loss, int N, int C, int splits, float pw, float rw,
+                     float a, float b, float smooth, int c0, hipStream_t s);
+void region_grad(const float* logits, const int64_t* target, const float* weight, const float* coef,
+                 const float* gup, float* grad, int N, int C, long HW, int ignore_index, int pix, float gamma,
+                 float pw, float rw, float a, float b, int c0, hipStream_t s);
 
 // optim.hip  (flat fp32 buffers; hyper = device fp32 array, see optim.hip for the layout)
 void adam_step(float* p, const float* g, float* m, float* v, const float* hyper, long n, int adamw,

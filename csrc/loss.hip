@@ -7,6 +7,9 @@
 //   bce_dice_*    : binary (num_class == 1) BCE-with-logits + per-sample soft Dice on the sigmoid
 //                   (SURVEY Appendix E.1): a per-sample reduction pass, then the gradient pass once the
 //                   sample's Dice sums are known.
+//   region_*      : softmax heads (num_class >= 2): CE | focal pixel term + per-sample, per-class soft
+//                   Dice | Tversky on the softmax; statistics pass, one-block finalize (coefficients and
+//                   loss stay on the device), gradient pass.
 // Partials are per block ([nblk][2] = {weighted loss sum, weight sum}); the host sums them.
 #include "common.h"
 #include "launchers.h"
@@ -310,6 +313,372 @@ __global__ __launch_bounds__(kBlock) void ohem_bwd_kernel(float* __restrict__ gr
     for (int c = 0; c < C; ++c) gx[c * HW] *= w;
   }
 }
+
+// ---- multi-class region losses (num_class >= 2): pixel term (CE or focal) + per-sample soft
+// Dice / Tversky on the softmax.  Two passes, grid (splits, N) each:
+//   region_stats_*  : part[n][b][2 + 3C] = {sum w*l, sum w, then (I, P, T) per class} of block b's slice
+//   region_finalize : one block sums the splits in a fixed order -> coef {num, den} per (n, c), the
+//                     batch's sum(w) at coef[2NC], and the loss scalar
+//   region_grad_*   : recomputes the softmax, reads coef and the upstream gradient from device memory
+// A pixel is valid iff t != ignore_index and 0 <= t < C (the ce_kernel rule).  No float atomics:
+// wave shuffle, then LDS, then one row per block, so every run adds in the same order.
+constexpr int kRegionPixNone = 0, kRegionPixCE = 1, kRegionPixFocal = 2;
+constexpr int kFinBlock = 1024;
+
+struct RegionPix {   // the pixel term of one valid pixel
+  float l;           // -(1 - p_t)^gamma log p_t
+  float G;           // dl/dx_k = G * ([k == t] - p_k)
+};
+
+// q = 1 - p_t (as the normalised sum over the other classes), lpt = log p_t = x_t - lse.
+// Focal needs gamma >= 1 (gamma == 0 is routed to CE by the caller).
+DEVI RegionPix region_pixel(int pix, float gamma, float q, float pt, float lpt) {
+  RegionPix r;
+  if (pix == kRegionPixFocal) {
+    // q^(gamma - 1): q == 0 gives exp2(-inf) = 0 for gamma > 1; gamma == 1 must not evaluate 0 * inf
+    const float pw1 = gamma == 2.f ? q : (gamma == 1.f ? 1.f : __builtin_amdgcn_exp2f((gamma - 1.f) * __log2f(q)));
+    const float f = pw1 * q;
+    r.l = -f * lpt;
+    r.G = gamma * pw1 * pt * lpt - f;
+  } else {
+    r.l = -lpt;
+    r.G = -1.f;
+  }
+  return r;
+}
+
+DEVI bool region_valid(long t, int C, int ignore_index) { return t != ignore_index && t >= 0 && t < C; }
+
+// one valid pixel, C classes in registers (every index static: no scratch)
+template <int C>
+DEVI void region_stats_px(const float (&x)[C], int t, float w, int pix, float gamma, float (&a)[2 + 3 * C]) {
+  float m = x[0];
+#pragma unroll
+  for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
+  float e[C], se = 0.f, so = 0.f, xt = 0.f, et = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    e[c] = __expf(x[c] - m);
+    se += e[c];
+    if (c == t) { xt = x[c]; et = e[c]; } else so += e[c];
+  }
+  const float inv = 1.f / se;
+  if (pix != kRegionPixNone) {
+    const RegionPix r = region_pixel(pix, gamma, so * inv, et * inv, (xt - m) - __logf(se));
+    a[0] += w * r.l;
+    a[1] += w;
+  }
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const float p = e[c] * inv;
+    a[2 + 3 * c + 1] += p;
+    if (c == t) { a[2 + 3 * c] += p; a[2 + 3 * c + 2] += 1.f; }
+  }
+}
+
+template <int C, bool VEC>
+__global__ __launch_bounds__(kBlock) void region_stats_kernel(const float* __restrict__ logits,
+                                                              const int64_t* __restrict__ target,
+                                                              const float* __restrict__ weight,
+                                                              float* __restrict__ part, long HW, int ignore_index,
+                                                              int pix, float gamma) {
+  constexpr int F = 2 + 3 * C;
+  __shared__ float red[F][kBlock / 64];
+  const int n = blockIdx.y;
+  const float* xs = logits + (long)n * C * HW;
+  const int64_t* ts = target + (long)n * HW;
+  float a[F];
+#pragma unroll
+  for (int k = 0; k < F; ++k) a[k] = 0.f;
+  if (VEC) {   // 4 consecutive pixels of this sample per lane (HW % 4 == 0: a group never leaves the image)
+    const long G = HW >> 2;
+    for (long g = (long)blockIdx.x * kBlock + threadIdx.x; g < G; g += (long)gridDim.x * kBlock) {
+      const longlong2 t01 = *reinterpret_cast<const longlong2*>(ts + 4 * g);
+      const longlong2 t23 = *reinterpret_cast<const longlong2*>(ts + 4 * g + 2);
+      const long tt[4] = {t01.x, t01.y, t23.x, t23.y};
+      float4 xv[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) xv[c] = *reinterpret_cast<const float4*>(xs + c * HW + 4 * g);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (!region_valid(tt[j], C, ignore_index)) continue;
+        float x[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) x[c] = j == 0 ? xv[c].x : (j == 1 ? xv[c].y : (j == 2 ? xv[c].z : xv[c].w));
+        region_stats_px<C>(x, (int)tt[j], weight ? weight[tt[j]] : 1.f, pix, gamma, a);
+      }
+    }
+  } else {
+    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < HW; i += (long)gridDim.x * kBlock) {
+      const long t = ts[i];
+      if (!region_valid(t, C, ignore_index)) continue;
+      float x[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) x[c] = xs[c * HW + i];
+      region_stats_px<C>(x, (int)t, weight ? weight[t] : 1.f, pix, gamma, a);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < F; ++k) {
+    const float w = wave_sum(a[k]);
+    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < F) {
+    float v = 0.f;
+    for (int w = 0; w < kBlock / 64; ++w) v += red[threadIdx.x][w];
+    part[((long)n * gridDim.x + blockIdx.x) * F + threadIdx.x] = v;
+  }
+}
+
+// any C <= kMaxC, one pixel per lane: lane c of each wave keeps class c's (I, P, T) in registers and
+// takes the wave's sum of every iteration (all lanes run every iteration; idle ones add zeros).
+__global__ __launch_bounds__(kBlock) void region_stats_generic_kernel(const float* __restrict__ logits,
+                                                                      const int64_t* __restrict__ target,
+                                                                      const float* __restrict__ weight,
+                                                                      float* __restrict__ part, int C, long HW,
+                                                                      int ignore_index, int pix, float gamma) {
+  __shared__ float red[kBlock / 64][kMaxC][3];
+  __shared__ float red2[2][kBlock / 64];
+  const int n = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int F = 2 + 3 * C;
+  const float* xs = logits + (long)n * C * HW;
+  const int64_t* ts = target + (long)n * HW;
+  float aI = 0.f, aP = 0.f, aT = 0.f, ls = 0.f, ws = 0.f;
+  for (long base = (long)blockIdx.x * kBlock; base < HW; base += (long)gridDim.x * kBlock) {
+    const long i = base + threadIdx.x;
+    const long t = i < HW ? ts[i] : -1;
+    const bool valid = i < HW && region_valid(t, C, ignore_index);
+    const float* xp = xs + (valid ? i : 0);
+    float m = -INFINITY;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, xp[c * HW]);
+    float se = 0.f, so = 0.f, xt = 0.f, et = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float v = xp[c * HW], e = __expf(v - m);
+      se += e;
+      if (c == t) { xt = v; et = e; } else so += e;
+    }
+    const float inv = 1.f / se;
+    if (valid && pix != kRegionPixNone) {
+      const float w = weight ? weight[t] : 1.f;
+      const RegionPix r = region_pixel(pix, gamma, so * inv, et * inv, (xt - m) - __logf(se));
+      ls += w * r.l;
+      ws += w;
+    }
+    for (int c = 0; c < C; ++c) {
+      const float p = valid ? __expf(xp[c * HW] - m) * inv : 0.f;
+      const bool y = valid && c == t;
+      const float sP = wave_sum(p), sI = wave_sum(y ? p : 0.f), sT = wave_sum(y ? 1.f : 0.f);
+      if (lane == c) { aP += sP; aI += sI; aT += sT; }
+    }
+  }
+  red[wv][lane][0] = aI; red[wv][lane][1] = aP; red[wv][lane][2] = aT;
+  ls = wave_sum(ls);
+  ws = wave_sum(ws);
+  if (lane == 0) { red2[0][wv] = ls; red2[1][wv] = ws; }
+  __syncthreads();
+  float* row = part + ((long)n * gridDim.x + blockIdx.x) * F;
+  if (threadIdx.x < 2) {
+    float v = 0.f;
+    for (int w = 0; w < kBlock / 64; ++w) v += red2[threadIdx.x][w];
+    row[threadIdx.x] = v;
+  }
+  if (threadIdx.x < 3 * C) {
+    const int c = threadIdx.x / 3, k = threadIdx.x - 3 * c;
+    float v = 0.f;
+    for (int w = 0; w < kBlock / 64; ++w) v += red[w][c][k];
+    row[2 + threadIdx.x] = v;
+  }
+}
+
+DEVI float block_sum_fin(float v, float* red) {   // kFinBlock threads, fixed order; every thread gets the total
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = 0.f;
+  for (int w = 0; w < kFinBlock / 64; ++w) s += red[w];
+  return s;
+}
+
+// one block: TI_nc = num / den with num = I + s, den = I + a (P - I) + b (T - I) + s;
+// loss = pw * sum(w l) / sum(w) [0 when no pixel is valid] + rw * (1 - mean_{n, c >= c0} TI_nc)
+__global__ __launch_bounds__(kFinBlock) void region_finalize_kernel(const float* __restrict__ part,
+                                                                     float* __restrict__ coef,
+                                                                     float* __restrict__ loss, int N, int C,
+                                                                     int splits, float pw, float rw, float a, float b,
+                                                                     float s, int c0) {
+  __shared__ float red[kFinBlock / 64];
+  const int F = 2 + 3 * C;
+  float ti = 0.f;
+  for (int idx = threadIdx.x; idx < N * C; idx += kFinBlock) {
+    const int n = idx / C, c = idx - n * C;
+    const float* p = part + (long)n * splits * F + 2 + 3 * c;
+    float I = 0.f, P = 0.f, T = 0.f;
+    for (int k = 0; k < splits; ++k) { I += p[(long)k * F]; P += p[(long)k * F + 1]; T += p[(long)k * F + 2]; }
+    const float num = I + s, den = I + a * (P - I) + b * (T - I) + s;
+    coef[2 * idx] = num;
+    coef[2 * idx + 1] = den;
+    if (c >= c0) ti += num / den;
+  }
+  float S = 0.f, W = 0.f;
+  for (int n = threadIdx.x; n < N; n += kFinBlock) {
+    const float* p = part + (long)n * splits * F;
+    for (int k = 0; k < splits; ++k) { S += p[(long)k * F]; W += p[(long)k * F + 1]; }
+  }
+  ti = block_sum_fin(ti, red);
+  S = block_sum_fin(S, red);
+  W = block_sum_fin(W, red);
+  if (threadIdx.x == 0) {
+    coef[2 * N * C] = W;
+    float l = 0.f;
+    if (pw != 0.f && W > 0.f) l += pw * (S / W);
+    if (rw != 0.f) l += rw * (1.f - ti / (float)(N * (C - c0)));
+    loss[0] = l;
+  }
+}
+
+// dTI/dp_c of one (n, c): k1 where y_c = 1, k0 where y_c = 0, both scaled by -rw / (N C')
+DEVI void region_k(const float* coef, int n, int C, int c, int N, float rw, float a, float b, int c0, float& k1,
+                   float& k0) {
+  k1 = k0 = 0.f;
+  if (rw == 0.f || c < c0) return;
+  const float num = coef[2 * (n * C + c)], den = coef[2 * (n * C + c) + 1];
+  const float sc = -rw / ((float)(N * (C - c0)) * den * den);
+  k1 = sc * (den - num * (1.f - b));
+  k0 = -sc * num * a;
+}
+
+// dx_k = g0 * (p_k (A_k - sum_c A_c p_c) + kp * G * ([k == t] - p_k)),  A_c = y_c ? k1_c : k0_c
+template <int C>
+DEVI void region_grad_px(const float (&x)[C], int t, float kp, int pix, float gamma, const float (&k1)[C],
+                         const float (&k0)[C], float g0, float (&g)[C]) {
+  float m = x[0];
+#pragma unroll
+  for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
+  float e[C], se = 0.f, so = 0.f, xt = 0.f, et = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    e[c] = __expf(x[c] - m);
+    se += e[c];
+    if (c == t) { xt = x[c]; et = e[c]; } else so += e[c];
+  }
+  const float inv = 1.f / se;
+  float kG = 0.f;
+  if (pix != kRegionPixNone) kG = kp * region_pixel(pix, gamma, so * inv, et * inv, (xt - m) - __logf(se)).G;
+  float dot = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) dot += (c == t ? k1[c] : k0[c]) * (e[c] * inv);
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const float p = e[c] * inv;
+    g[c] = g0 * (p * ((c == t ? k1[c] : k0[c]) - dot) + kG * ((c == t ? 1.f : 0.f) - p));
+  }
+}
+
+template <int C, bool VEC>
+__global__ __launch_bounds__(kBlock) void region_grad_kernel(const float* __restrict__ logits,
+                                                             const int64_t* __restrict__ target,
+                                                             const float* __restrict__ weight,
+                                                             const float* __restrict__ coef,
+                                                             const float* __restrict__ gup, float* __restrict__ grad,
+                                                             int N, long HW, int ignore_index, int pix, float gamma,
+                                                             float pw, float rw, float a, float b, int c0) {
+  const int n = blockIdx.y;
+  const float* xs = logits + (long)n * C * HW;
+  const int64_t* ts = target + (long)n * HW;
+  float* gs = grad + (long)n * C * HW;
+  const float g0 = gup[0], W = coef[2 * N * C];
+  const float kpw = (pix != kRegionPixNone && W > 0.f) ? pw / W : 0.f;
+  float k1[C], k0[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) region_k(coef, n, C, c, N, rw, a, b, c0, k1[c], k0[c]);
+  if (VEC) {
+    const long G = HW >> 2;
+    for (long g = (long)blockIdx.x * kBlock + threadIdx.x; g < G; g += (long)gridDim.x * kBlock) {
+      const longlong2 t01 = *reinterpret_cast<const longlong2*>(ts + 4 * g);
+      const longlong2 t23 = *reinterpret_cast<const longlong2*>(ts + 4 * g + 2);
+      const long tt[4] = {t01.x, t01.y, t23.x, t23.y};
+      float4 xv[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) xv[c] = *reinterpret_cast<const float4*>(xs + c * HW + 4 * g);
+      float o[C][4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float x[C], gg[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          x[c] = j == 0 ? xv[c].x : (j == 1 ? xv[c].y : (j == 2 ? xv[c].z : xv[c].w));
+          gg[c] = 0.f;
+        }
+        if (region_valid(tt[j], C, ignore_index))
+          region_grad_px<C>(x, (int)tt[j], kpw * (weight ? weight[tt[j]] : 1.f), pix, gamma, k1, k0, g0, gg);
+#pragma unroll
+        for (int c = 0; c < C; ++c) o[c][j] = gg[c];
+      }
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        *reinterpret_cast<float4*>(gs + c * HW + 4 * g) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
+    }
+  } else {
+    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < HW; i += (long)gridDim.x * kBlock) {
+      const long t = ts[i];
+      float x[C], gg[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) { x[c] = xs[c * HW + i]; gg[c] = 0.f; }
+      if (region_valid(t, C, ignore_index))
+        region_grad_px<C>(x, (int)t, kpw * (weight ? weight[t] : 1.f), pix, gamma, k1, k0, g0, gg);
+#pragma unroll
+      for (int c = 0; c < C; ++c) gs[c * HW + i] = gg[c];
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void region_grad_generic_kernel(
+    const float* __restrict__ logits, const int64_t* __restrict__ target, const float* __restrict__ weight,
+    const float* __restrict__ coef, const float* __restrict__ gup, float* __restrict__ grad, int N, int C, long HW,
+    int ignore_index, int pix, float gamma, float pw, float rw, float a, float b, int c0) {
+  __shared__ float kk[kMaxC][2];
+  const int n = blockIdx.y;
+  const float* xs = logits + (long)n * C * HW;
+  const int64_t* ts = target + (long)n * HW;
+  float* gs = grad + (long)n * C * HW;
+  if (threadIdx.x < C) region_k(coef, n, C, threadIdx.x, N, rw, a, b, c0, kk[threadIdx.x][0], kk[threadIdx.x][1]);
+  __syncthreads();
+  const float g0 = gup[0], W = coef[2 * N * C];
+  const float kpw = (pix != kRegionPixNone && W > 0.f) ? pw / W : 0.f;
+  for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < HW; i += (long)gridDim.x * kBlock) {
+    const long t = ts[i];
+    const float* xp = xs + i;
+    float* gp = gs + i;
+    if (!region_valid(t, C, ignore_index)) {
+      for (int c = 0; c < C; ++c) gp[c * HW] = 0.f;
+      continue;
+    }
+    float m = -INFINITY;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, xp[c * HW]);
+    float se = 0.f, so = 0.f, xt = 0.f, et = 0.f, dot = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float v = xp[c * HW], e = __expf(v - m);
+      se += e;
+      dot += kk[c][c == t ? 0 : 1] * e;
+      if (c == t) { xt = v; et = e; } else so += e;
+    }
+    const float inv = 1.f / se;
+    dot *= inv;
+    float kG = 0.f;
+    if (pix != kRegionPixNone)
+      kG = kpw * (weight ? weight[t] : 1.f) * region_pixel(pix, gamma, so * inv, et * inv, (xt - m) - __logf(se)).G;
+    for (int c = 0; c < C; ++c) {
+      const float p = __expf(xp[c * HW] - m) * inv;
+      gp[c * HW] = g0 * (p * (kk[c][c == t ? 0 : 1] - dot) + kG * ((c == t ? 1.f : 0.f) - p));
+    }
+  }
+}
+
+bool region_vec_ok(const void* x, const void* t, const void* g, long HW) {
+  return HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)t | (uintptr_t)g) & 15) == 0;
+}
 }  // namespace
 
 long ce_blocks(long P) {
@@ -372,4 +741,60 @@ void ohem_backward(float* grad, const float* pix_loss, const unsigned* state, co
                    hipStream_t s) {
   hipLaunchKernelGGL(ohem_bwd_kernel, dim3(ce_blocks((long)N * HW)), dim3(kBlock), 0, s, grad, pix_loss, state, gup,
                      N, C, HW);
+}
+
+int region_max_classes() { return kMaxC; }
+
+int region_splits(long HW) {
+  long b = (HW + kBlock * 16 - 1) / (kBlock * 16);
+  if (b > 256) b = 256;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+void region_stats(const float* logits, const int64_t* target, const float* weight, float* part, int N, int C,
+                  long HW, int ignore_index, int pix, float gamma, hipStream_t s) {
+  const dim3 grid(region_splits(HW), N), block(kBlock);
+  const bool vec = region_vec_ok(logits, target, nullptr, HW);
+#define REGION_STATS(CC)                                                                                          \
+  if (vec)                                                                                                        \
+    hipLaunchKernelGGL((region_stats_kernel<CC, true>), grid, block, 0, s, logits, target, weight, part, HW,      \
+                       ignore_index, pix, gamma);                                                                 \
+  else                                                                                                            \
+    hipLaunchKernelGGL((region_stats_kernel<CC, false>), grid, block, 0, s, logits, target, weight, part, HW,     \
+                       ignore_index, pix, gamma)
+  if (C == 2) { REGION_STATS(2); }
+  else if (C == 3) { REGION_STATS(3); }
+  else if (C == 4) { REGION_STATS(4); }
+  else
+    hipLaunchKernelGGL(region_stats_generic_kernel, grid, block, 0, s, logits, target, weight, part, C, HW,
+                       ignore_index, pix, gamma);
+#undef REGION_STATS
+}
+
+void region_finalize(const float* part, float* coef, float* loss, int N, int C, int splits, float pw, float rw,
+                     float a, float b, float smooth, int c0, hipStream_t s) {
+  hipLaunchKernelGGL(region_finalize_kernel, dim3(1), dim3(kFinBlock), 0, s, part, coef, loss, N, C, splits, pw, rw,
+                     a, b, smooth, c0);
+}
+
+void region_grad(const float* logits, const int64_t* target, const float* weight, const float* coef,
+                 const float* gup, float* grad, int N, int C, long HW, int ignore_index, int pix, float gamma,
+                 float pw, float rw, float a, float b, int c0, hipStream_t s) {
+  const dim3 grid(region_splits(HW), N), block(kBlock);
+  const bool vec = region_vec_ok(logits, target, grad, HW);
+#define REGION_GRAD(CC)                                                                                           \
+  if (vec)                                                                                                        \
+    hipLaunchKernelGGL((region_grad_kernel<CC, true>), grid, block, 0, s, logits, target, weight, coef, gup,      \
+                       grad, N, HW, ignore_index, pix, gamma, pw, rw, a, b, c0);                                  \
+  else                                                                                                            \
+    hipLaunchKernelGGL((region_grad_kernel<CC, false>), grid, block, 0, s, logits, target, weight, coef, gup,     \
+                       grad, N, HW, ignore_index, pix, gamma, pw, rw, a, b, c0)
+  if (C == 2) { REGION_GRAD(2); }
+  else if (C == 3) { REGION_GRAD(3); }
+  else if (C == 4) { REGION_GRAD(4); }
+  else
+    hipLaunchKernelGGL(region_grad_generic_kernel, grid, block, 0, s, logits, target, weight, coef, gup, grad, N, C,
+                       HW, ignore_index, pix, gamma, pw, rw, a, b, c0);
+#undef REGION_GRAD
 }

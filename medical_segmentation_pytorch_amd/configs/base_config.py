@@ -59,6 +59,14 @@ class BaseConfig:
         self.class_weights = None
         self.ohem_thrs = 0.7
         self.reduction = 'mean'
+        # softmax-head overlap / focal losses (core.loss.RegionLoss; absent from the reference)
+        self.loss_pixel_weight = 1.0   # weight of the ce / focal term
+        self.loss_region_weight = 1.0  # weight of the dice / tversky term
+        self.dice_smooth = 1.0
+        self.dice_ignore_background = False   # leave class 0 out of the region mean
+        self.tversky_alpha = 0.3       # false-positive weight
+        self.tversky_beta = 0.7        # false-negative weight
+        self.focal_gamma = 2.0         # 0 (plain ce) or >= 1
 
         # Scheduler
         self.lr_policy = 'cos_warmup'

@@ -54,7 +54,15 @@ def get_parser():
     _flag(p, 'blend_prediction', action='store_false')
     _flag(p, 'blend_alpha', type=float)
     # Loss
-    _flag(p, 'loss_type', type=str, choices=['ce', 'ohem', 'bce', 'dice', 'bce_dice', 'ce_dice'])
+    _flag(p, 'loss_type', type=str, choices=['ce', 'ohem', 'bce', 'dice', 'bce_dice', 'tversky', 'focal', 'ce_dice',
+                                             'ce_tversky', 'focal_dice', 'focal_tversky'])
+    _flag(p, 'loss_pixel_weight', type=float)
+    _flag(p, 'loss_region_weight', type=float)
+    _flag(p, 'dice_smooth', type=float)
+    _flag(p, 'dice_ignore_background', action='store_true')
+    _flag(p, 'tversky_alpha', type=float)
+    _flag(p, 'tversky_beta', type=float)
+    _flag(p, 'focal_gamma', type=float)
     _flag(p, 'class_weights', type=float, nargs='+')
     _flag(p, 'ohem_thrs', type=float)
     _flag(p, 'reduction', type=str, choices=['mean', 'sum', 'none'])

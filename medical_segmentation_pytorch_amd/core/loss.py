@@ -2,7 +2,9 @@
 
 On a ROCm device with the HIP extension the CE / OHEM / KD-KL losses run the fused single-pass
 kernels of ``csrc/loss.hip`` (loss + gradient in one pass); elsewhere plain PyTorch with identical
-semantics.  Added (north star): ``'bce_dice'`` for ``num_class == 1``.
+semantics.  Added (north star): ``'bce_dice'`` for ``num_class == 1``, and for
+softmax heads (``num_class >= 2``) the overlap / focal family of :class:`RegionLoss`: ``dice``,
+``tversky``, ``focal``, ``ce_dice``, ``ce_tversky``, ``focal_dice``, ``focal_tversky``.
 """
 from __future__ import annotations
 
@@ -74,18 +76,102 @@ class BceDiceLoss(nn.Module):
         return self.bw * bce + self.dw * dice
 
 
+class RegionLoss(nn.Module):
+    """Softmax-head (``num_class >= 2``) loss: ``pixel_weight * L_pix + region_weight * L_reg``.
+
+    A pixel is valid iff ``label != ignore_index and 0 <= label < C``; with ``p = softmax(logits)``,
+    ``y_c = [label == c]`` and ``w_c = weight[c]`` (or 1):
+
+    * ``L_pix = sum_valid(w_t l) / sum_valid(w_t)`` over the batch, ``l = -log p_t`` (``pixel='ce'``) or
+      ``-(1 - p_t)^gamma log p_t`` (``'focal'``; ``gamma`` is 0 -- exactly CE -- or >= 1, since the gradient
+      of a fractional power below 1 is unbounded at ``p_t -> 1``).  With no valid pixel ``L_pix`` is 0
+      with zero gradient (``F.cross_entropy`` gives NaN there).
+    * ``L_reg = 1 - mean_{n, c} TI_nc`` with, over the valid pixels of sample ``n``, ``I = sum p_c y_c``,
+      ``P = sum p_c``, ``T = sum y_c`` and ``TI = (I + s) / (I + a (P - I) + b (T - I) + s)``:
+      ``region='tversky'`` uses ``a = alpha``, ``b = beta``, ``s = smooth``; ``'dice'`` is ``a = b = 0.5``,
+      ``s = smooth / 2``, i.e. ``(2I + smooth) / (P + T + smooth)`` as in :class:`BceDiceLoss`.
+      ``ignore_background`` leaves class 0 out of the mean.
+
+    The region sums are per sample, so nothing is exchanged across DDP ranks: every rank's loss is the mean
+    over its own samples, the same semantics as ``ce``.  On a ROCm device with the HIP extension this is
+    ``ops.losses.region_loss`` (fused, deterministic, graph-capturable); elsewhere the plain-torch form
+    below, in the input's floating dtype."""
+
+    def __init__(self, pixel='ce', region='dice', ignore_index=255, weight=None, pixel_weight=1.0, region_weight=1.0,
+                 smooth=1.0, alpha=0.3, beta=0.7, gamma=2.0, ignore_background=False):
+        super().__init__()
+        if pixel not in (None, 'ce', 'focal') or region not in (None, 'dice', 'tversky') or pixel == region:
+            raise ValueError(f'RegionLoss: pixel={pixel!r} region={region!r}')
+        if pixel == 'focal' and not (gamma == 0 or gamma >= 1):
+            raise ValueError(f'focal_gamma must be 0 or >= 1, got {gamma}')
+        self.pixel, self.region, self.ignore_index = pixel, region, ignore_index
+        self.pw, self.rw = float(pixel_weight), float(region_weight)
+        self.smooth, self.alpha, self.beta, self.gamma = float(smooth), float(alpha), float(beta), float(gamma)
+        self.ignore_background = bool(ignore_background)
+        self.register_buffer('weight', weight if weight is None else weight.float())
+
+    def forward(self, logits, labels):
+        if _fused_ok(logits):
+            from ..ops.losses import region_loss
+            return region_loss(logits.float(), labels, self.weight, self.ignore_index, self.pixel, self.region,
+                               self.pw, self.rw, self.smooth, self.alpha, self.beta, self.gamma,
+                               self.ignore_background)
+        x = logits if logits.dtype in (torch.float32, torch.float64) else logits.float()
+        C = x.shape[1]
+        valid = (labels != self.ignore_index) & (labels >= 0) & (labels < C)
+        vf = valid.unsqueeze(1).to(x.dtype)
+        y = F.one_hot(torch.where(valid, labels, torch.zeros_like(labels)), C).movedim(-1, 1).to(x.dtype) * vf
+        p = F.softmax(x, 1)
+        loss = x.new_zeros(())
+        if self.pixel is not None:
+            logpt = (F.log_softmax(x, 1) * y).sum(1)               # x_t - lse; 0 on ignored pixels
+            l = -logpt
+            if self.pixel == 'focal' and self.gamma != 0:
+                l = l * (p * (vf - y)).sum(1) ** self.gamma        # 1 - p_t as the sum over the other classes
+            w = vf[:, 0] if self.weight is None else (y * self.weight.to(x.dtype).view(1, C, 1, 1)).sum(1)
+            W = w.sum()
+            loss = loss + self.pw * torch.where(W > 0, (w * l).sum() / torch.where(W > 0, W, torch.ones_like(W)),
+                                                torch.zeros_like(W))
+        if self.region is not None:
+            a, b, s = (0.5, 0.5, 0.5 * self.smooth) if self.region == 'dice' else (self.alpha, self.beta, self.smooth)
+            inter, ps, ts = (p * y).sum((2, 3)), (p * vf).sum((2, 3)), y.sum((2, 3))
+            ti = (inter + s) / (inter + a * (ps - inter) + b * (ts - inter) + s)
+            loss = loss + self.rw * (1 - ti[:, 1 if self.ignore_background else 0:].mean())
+        return loss
+
+
+_PIXEL_TERMS, _REGION_TERMS = ('ce', 'focal'), ('dice', 'tversky')
+REGION_LOSS_TYPES = ('dice', 'tversky', 'focal', 'ce_dice', 'ce_tversky', 'focal_dice', 'focal_tversky')
+
+
 def get_loss_fn(config, device):
     weights = None if config.class_weights is None else torch.tensor(config.class_weights, dtype=torch.float32,
                                                                       device=device)
-    if config.loss_type == 'ce':
+    lt = config.loss_type
+    if lt == 'ce':
         return CrossEntropyLoss(ignore_index=config.ignore_index, reduction=config.reduction, weight=weights)
-    if config.loss_type == 'ohem':
+    if lt == 'ohem':
         return OhemCELoss(thresh=config.ohem_thrs, ignore_index=config.ignore_index)
-    if config.loss_type in ('bce_dice', 'bce', 'dice'):
-        bw = 0.0 if config.loss_type == 'dice' else 1.0
-        dw = 0.0 if config.loss_type == 'bce' else 1.0
+    multi = config.num_class >= 2
+    if lt in ('bce_dice', 'bce', 'dice') and not multi:
+        bw = 0.0 if lt == 'dice' else 1.0
+        dw = 0.0 if lt == 'bce' else 1.0
         return BceDiceLoss(bw, dw)
-    raise NotImplementedError(f'Unsupport loss type: {config.loss_type}')
+    if lt in ('bce_dice', 'bce'):
+        raise ValueError(f"loss_type '{lt}' is for a one-channel sigmoid head, but num_class = {config.num_class}; "
+                         f"use one of {REGION_LOSS_TYPES}")
+    if lt in REGION_LOSS_TYPES:
+        if not multi:
+            raise ValueError(f"loss_type '{lt}' needs a softmax head, but num_class = {config.num_class}; "
+                             f"use 'bce', 'dice' or 'bce_dice'")
+        terms = lt.split('_')
+        pixel = next((k for k in terms if k in _PIXEL_TERMS), None)
+        region = next((k for k in terms if k in _REGION_TERMS), None)
+        return RegionLoss(pixel, region, ignore_index=config.ignore_index, weight=weights,
+                          pixel_weight=config.loss_pixel_weight, region_weight=config.loss_region_weight,
+                          smooth=config.dice_smooth, alpha=config.tversky_alpha, beta=config.tversky_beta,
+                          gamma=config.focal_gamma, ignore_background=config.dice_ignore_background)
+    raise NotImplementedError(f'Unsupport loss type: {lt}')
 
 
 def kd_loss_fn(config, outputs, outputsT):

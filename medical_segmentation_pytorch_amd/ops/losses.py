@@ -12,6 +12,12 @@
 * :func:`bce_dice` == ``bw * BCEWithLogits + dw * (1 - mean_n soft-Dice_n)`` for binary heads
   (``num_class == 1``): a per-sample reduction kernel in forward, the gradient
   kernel in backward (it needs the sample's Dice sums), upstream gradient read on the device.
+* :func:`region_loss` == ``pw * pixel + rw * region`` for softmax heads (``num_class >= 2``; the
+  plain-torch form is ``core.loss.RegionLoss``): pixel term CE or focal (weighted mean over the valid
+  pixels), region term per-sample soft Dice / Tversky on the softmax.  Forward is the per-sample
+  statistics pass plus a one-block finalize (coefficient table and loss scalar stay on the device);
+  backward is one gradient pass that recomputes the softmax.  No atomics, no host read: bitwise
+  repeatable and graph-capturable like the others.
 """
 from __future__ import annotations
 
@@ -167,3 +173,54 @@ class _BCEDice(torch.autograd.Function):
 
 def bce_dice(logits, target, bce_weight=1.0, dice_weight=1.0, smooth=1.0):
     return _BCEDice.apply(logits, target, float(bce_weight), float(dice_weight), float(smooth))
+
+
+_PIX = {None: 0, 'ce': 1, 'focal': 2}
+
+
+class _Region(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, pix, gamma, pw, rw, a, b, smooth, c0):
+        C = require()
+        x = logits.contiguous().float()
+        t = target.contiguous().long()
+        n, c, h, w = x.shape
+        dev = x.device
+        part = torch.empty(n, C.region_splits(h * w), 2 + 3 * c, dtype=torch.float32, device=dev)
+        coef = torch.empty(2 * n * c + 1, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        C.region_fwd(x, t, weight, part, coef, loss, ignore_index, pix, gamma, pw, rw, a, b, smooth, c0)
+        ctx.save_for_backward(x, t, coef, weight)
+        ctx.args = (ignore_index, pix, gamma, pw, rw, a, b, c0)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t, coef, weight = ctx.saved_tensors
+        grad = torch.empty_like(x)
+        require().region_grad(x, t, weight, coef, g.detach().float().reshape(1).contiguous(), grad, *ctx.args)
+        return (grad,) + (None,) * 11
+
+
+def region_loss(logits, target, weight=None, ignore_index=255, pixel='ce', region='dice', pixel_weight=1.0,
+                region_weight=1.0, smooth=1.0, alpha=0.3, beta=0.7, gamma=2.0, ignore_background=False):
+    """``pixel_weight * L_pix + region_weight * L_reg`` on fp32 NCHW logits and int64 ``[N, H, W]`` labels.
+
+    ``pixel``: None | 'ce' | 'focal' (``gamma`` 0 or >= 1; 0 is CE); ``region``: None | 'dice' | 'tversky'
+    (``alpha`` / ``beta`` weigh false positives / negatives; Dice is Tversky(0.5, 0.5) with ``smooth / 2``,
+    i.e. ``(2I + smooth) / (P + T + smooth)``).  A pixel counts iff ``target != ignore_index`` and
+    ``0 <= target < C``.  The region sums are per sample, so nothing is exchanged across DDP ranks: each
+    rank's loss is the mean over its own samples, the same semantics as ``cross_entropy``."""
+    if pixel not in _PIX or region not in (None, 'dice', 'tversky') or (pixel is None and region is None):
+        raise ValueError(f'region_loss: pixel={pixel!r} region={region!r}')
+    gamma = float(gamma)
+    if pixel == 'focal' and not (gamma == 0.0 or gamma >= 1.0):
+        raise ValueError(f'focal_gamma must be 0 or >= 1, got {gamma}')
+    pix = 1 if pixel == 'focal' and gamma == 0.0 else _PIX[pixel]
+    a, b, s = (0.5, 0.5, 0.5 * smooth) if region == 'dice' else (alpha, beta, smooth)
+    if weight is not None:
+        weight = weight.to(device=logits.device, dtype=torch.float32).contiguous()
+    return _Region.apply(logits, target, weight, int(ignore_index), pix, gamma if pix == 2 else 0.0,
+                         float(pixel_weight) if pixel is not None else 0.0,
+                         float(region_weight) if region is not None else 0.0, float(a), float(b), float(s),
+                         1 if ignore_background else 0)
