@@ -763,6 +763,81 @@ void confmat_update_t(const at::Tensor& logits, const at::Tensor& target, const 
                  cur_stream());
 }
 
+// ---- boundary metrics (surface.hip)
+#define CHECK_U8(t) CHECK_DEV(t); TORCH_CHECK((t).scalar_type() == at::kByte, #t " must be uint8")
+#define CHECK_I32(t) CHECK_DEV(t); TORCH_CHECK((t).scalar_type() == at::kInt, #t " must be int32")
+
+static void surface_dims_check(int64_t B, int64_t H, int64_t W) {
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= kEdtMaxDim && W <= kEdtMaxDim, "distance transform: H and W must be in [1, ",
+              kEdtMaxDim, "], got ", H, " x ", W);
+  TORCH_CHECK(B >= 1 && B * H <= 2147483647LL, "distance transform: too many rows in one call (", B, " images)");
+}
+
+void surface_labels_t(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& lab,
+                      int64_t ignore_index) {
+  CHECK_F32(logits); CHECK_I64(target); CHECK_U8(lab);
+  TORCH_CHECK(logits.dim() == 4, "logits must be NCHW");
+  const int64_t N = logits.size(0), C = logits.size(1), HW = logits.size(2) * logits.size(3);
+  TORCH_CHECK(C >= 2 && C <= kSurfMaxClasses, "surface metrics: num_class must be in [2, ", kSurfMaxClasses, "]");
+  TORCH_CHECK(N >= 1 && HW >= 1 && target.numel() == N * HW && lab.numel() == 2 * N * HW,
+              "target must be [N, H, W] and lab [2, N, H, W]");
+  surf_labels(f32(logits), target.data_ptr<int64_t>(), lab.data_ptr<uint8_t>(), (int)N, (int)C, HW,
+              (int)ignore_index, cur_stream());
+}
+
+void surface_boundary_t(const at::Tensor& lab, const at::Tensor& bnd, int64_t K) {
+  CHECK_U8(lab); CHECK_U8(bnd);
+  TORCH_CHECK(lab.dim() == 3, "lab must be [B, H, W]");
+  const int64_t B = lab.size(0), H = lab.size(1), W = lab.size(2);
+  surface_dims_check(B, H, W);
+  TORCH_CHECK(K >= 1 && K < kSurfMaxClasses && bnd.numel() == B * K * H * W, "bnd must be [B, K, H, W]");
+  surf_boundary(lab.data_ptr<uint8_t>(), bnd.data_ptr<uint8_t>(), B, (int)K, (int)H, (int)W, cur_stream());
+}
+
+void edt_sq_t(const at::Tensor& mask, const at::Tensor& d2, const c10::optional<at::Tensor>& sel, int64_t half) {
+  CHECK_U8(mask); CHECK_I32(d2);
+  TORCH_CHECK(mask.dim() == 3, "mask must be [B, H, W]");
+  const int64_t B = mask.size(0), H = mask.size(1), W = mask.size(2);
+  surface_dims_check(B, H, W);
+  TORCH_CHECK(d2.numel() == mask.numel(), "d2 must be shaped like mask");
+  const uint8_t* sp = nullptr;
+  if (sel.has_value() && sel->defined()) {
+    CHECK_U8(*sel);
+    TORCH_CHECK(sel->numel() == mask.numel() && half >= 0 && half < B, "sel must be shaped like mask, half in [0, B)");
+    sp = sel->data_ptr<uint8_t>();
+  }
+  edt_sq(mask.data_ptr<uint8_t>(), d2.data_ptr<int32_t>(), sp, half, B, (int)H, (int)W, cur_stream());
+}
+
+void surface_reduce_t(const at::Tensor& d2, const at::Tensor& stats, const at::Tensor& sums, int64_t vmax,
+                      int64_t tol2) {
+  CHECK_I32(d2); CHECK_I64(stats); CHECK_F64(sums);
+  TORCH_CHECK(d2.dim() == 3, "d2 must be [B, H, W]");
+  const int64_t B = d2.size(0), HW = d2.size(1) * d2.size(2);
+  TORCH_CHECK(B >= 1 && B <= 2147483647LL && HW >= 1, "d2 must be [B, H, W]");
+  TORCH_CHECK(stats.numel() == B * kSurfStatCols && sums.numel() == B, "stats must be [B, 4], sums [B]");
+  TORCH_CHECK(vmax >= 0 && vmax < kEdtNone && tol2 >= 0 && tol2 < kEdtNone, "vmax / tol2 out of range");
+  surf_reduce(d2.data_ptr<int32_t>(), stats.data_ptr<int64_t>(), sums.data_ptr<double>(), B, HW, (int)vmax, (int)tol2,
+              cur_stream());
+}
+
+void surface_finalize_t(const at::Tensor& stats, const at::Tensor& sums, const at::Tensor& sum,
+                        const at::Tensor& count, const at::Tensor& onesided,
+                        const c10::optional<at::Tensor>& per_image, int64_t N, int64_t K, int64_t H, int64_t W) {
+  CHECK_I64(stats); CHECK_F64(sums); CHECK_F64(sum); CHECK_I64(count); CHECK_I64(onesided);
+  TORCH_CHECK(N >= 1 && K >= 1 && N <= 2147483647LL && K < kSurfMaxClasses && H >= 1 && W >= 1);
+  TORCH_CHECK(stats.numel() == 2 * N * K * kSurfStatCols && sums.numel() == 2 * N * K, "stats [2, N, K, 4], sums [2, N, K]");
+  TORCH_CHECK(sum.numel() == 3 * K && count.numel() == K && onesided.numel() == K, "state: sum [3, K], counts [K]");
+  double* pi = nullptr;
+  if (per_image.has_value() && per_image->defined()) {
+    CHECK_F64(*per_image);
+    TORCH_CHECK(per_image->numel() == N * K * 3, "per_image must be [N, K, 3]");
+    pi = per_image->data_ptr<double>();
+  }
+  surf_finalize(stats.data_ptr<int64_t>(), sums.data_ptr<double>(), sum.data_ptr<double>(), count.data_ptr<int64_t>(),
+                onesided.data_ptr<int64_t>(), pi, (int)N, (int)K, (int)H, (int)W, cur_stream());
+}
+
 
 // ---- decoder-hub ops (decoder.hip)
 void resize_bilinear_t(const at::Tensor& x, const at::Tensor& y, double sh, double sw, bool align, bool accum,
@@ -1265,6 +1340,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("amp_update", &amp_update_t);
   m.def("ema_update", &ema_update_t);
   m.def("confmat_update", &confmat_update_t);
+  m.def("surface_labels", &surface_labels_t);
+  m.def("surface_boundary", &surface_boundary_t);
+  m.def("edt_sq", &edt_sq_t, py::arg("mask"), py::arg("d2"), py::arg("sel") = py::none(), py::arg("half") = 0);
+  m.def("surface_reduce", &surface_reduce_t);
+  m.def("surface_finalize", &surface_finalize_t, py::arg("stats"), py::arg("sums"), py::arg("sum"), py::arg("count"),
+        py::arg("onesided"), py::arg("per_image"), py::arg("N"), py::arg("K"), py::arg("H"), py::arg("W"));
+  m.attr("EDT_MAX_DIM") = kEdtMaxDim;
+  m.attr("EDT_NONE") = kEdtNone;
   m.def("resize_bilinear", &resize_bilinear_t, py::arg("x"), py::arg("y"), py::arg("sh"), py::arg("sw"),
         py::arg("align"), py::arg("accum") = false, py::arg("backward") = false);
   m.def("nc_sums_blocks", &nc_sums_blocks_t);

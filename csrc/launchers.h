@@ -266,6 +266,30 @@ void bilinear_resize(const float* x, float* y, long NC, int IH, int IW, int OH, 
                      hipStream_t s);
 void colorize(const float* logits, const uint8_t* lut, uint8_t* rgb, int N, int C, long HW, hipStream_t s);
 
+// surface.hip: boundary metrics (HD95 / ASSD / NSD) on an exact integer squared Euclidean distance transform.
+// Images are uint8 [B][H][W] planes; H, W <= kEdtMaxDim.  A map without any set pixel is kEdtNone everywhere.
+constexpr int kEdtMaxDim = 16384;
+constexpr int kEdtNone = 2147483647;
+constexpr int kSurfMaxClasses = 255;   // label 255 = "in no class" (ignored / out-of-range target)
+constexpr int kSurfStatCols = 4;       // per (direction, n, class): |D|, #{d2 <= T}, d2 at floor / ceil of the q95 rank
+// lab [2][N][HW]: plane 0 the per-pixel argmax (first maximum wins), plane 1 the target; 255 where the target is
+// ignore_index or outside [0, C) (in both planes)
+void surf_labels(const float* logits, const int64_t* target, uint8_t* lab, int N, int C, long HW, int ignore_index,
+                 hipStream_t s);
+// bnd [B][K][HW]: pixel of class k + 1 with a 4-neighbour (outside the image counts) of another label
+void surf_boundary(const uint8_t* lab, uint8_t* bnd, long B, int K, int H, int W, hipStream_t s);
+// d2 [B][HW] = squared distance to the nearest nonzero pixel of mask [B][HW] (column scan, then row minimum).
+// sel (nullable, [B][HW]): only pixels where image (b + half) % B of sel is nonzero are evaluated, the rest get -1.
+void edt_sq(const uint8_t* mask, int32_t* d2, const uint8_t* sel, long half, long B, int H, int W, hipStream_t s);
+// Per image b of d2 [B][HW] (entries < 0 are no members; d2 is compacted in place, i.e. destroyed):
+// stats [B][kSurfStatCols] and sums [B] = sum of sqrt(d2) in fp64 (fixed order); vmax = H*H + W*W, tol2 = T
+void surf_reduce(int32_t* d2, int64_t* stats, double* sums, long B, long HW, int vmax, int tol2, hipStream_t s);
+// stats / sums [2][N][K] (the two directions; every value is symmetric in them) -> per-class state: sum [3][K]
+// (hd95, assd, nsd) fp64, count [K], onesided [K]; images are added in n order by one thread per class.
+// per_image (nullable) [N][K][3].
+void surf_finalize(const int64_t* stats, const double* sums, double* sum, int64_t* count, int64_t* onesided,
+                   double* per_image, int N, int K, int H, int W, hipStream_t s);
+
 // decoder.hip: smp decoder-hub ops (bilinear resize, GroupNorm, adaptive pooling, depthwise conv)
 void resize_bilinear_fwd(const uint16_t* x, uint16_t* y, int N, int IH, int IW, int OH, int OW, int Cp, float sh,
                          float sw, int align, int accum, hipStream_t s);

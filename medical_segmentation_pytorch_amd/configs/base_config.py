@@ -39,6 +39,7 @@ class BaseConfig:
 
         # Validating
         self.metrics = ['dice']        # the first one drives best-checkpoint selection
+        self.nsd_tolerance = 2.0       # pixels: the 'nsd' (surface Dice) metric counts boundary pixels this close
         self.val_bs = 16
         self.begin_val_epoch = 0
         self.val_interval = 1
@@ -169,6 +170,9 @@ class BaseConfig:
         """Derive dependent fields (reference base_config.py:106-123).  Fields this pass derived
         itself are re-derived on a later call (after CLI overrides); user-set values are kept."""
         assert len(self.metrics) > 0
+        if self.metrics[0] in ('hd95', 'assd'):
+            raise ValueError(f"metrics[0] drives best-checkpoint selection as higher-is-better; '{self.metrics[0]}' is "
+                             f"a distance (lower is better) -- put 'dice', 'iou' or 'nsd' first")
         auto = getattr(self, '_auto_derived', set())
 
         def derive(name, value, cond):

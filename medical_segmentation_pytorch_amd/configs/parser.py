@@ -40,6 +40,7 @@ def get_parser():
     _flag(p, 'aux_coef', type=float, nargs='+')
     # Validating
     _flag(p, 'metrics', type=str, nargs='+')
+    _flag(p, 'nsd_tolerance', type=float)
     _flag(p, 'val_bs', type=int)
     _flag(p, 'begin_val_epoch', type=int)
     _flag(p, 'val_interval', type=int)

@@ -43,6 +43,13 @@ def _tqdm(it, enable):
         return it
 
 
+def _finite_or_none(v):
+    """nan / inf -> None, so val_history.json stays strict JSON (a boundary metric with nothing scored is nan)."""
+    if isinstance(v, list):
+        return [_finite_or_none(x) for x in v]
+    return v if v == v and abs(v) != float('inf') else None
+
+
 class SegTrainer(BaseTrainer):
     def __init__(self, config):
         super().__init__(config)
@@ -212,6 +219,7 @@ class SegTrainer(BaseTrainer):
     @torch.no_grad()
     def validate(self, config, loader, val_best=False):
         self.config_ref = config
+        t_val = time.perf_counter()
         pbar = _tqdm(loader, self.main_rank and config.progress_bar)
         for images, masks in pbar:
             images = images.to(self.device, dtype=torch.float32)
@@ -242,6 +250,10 @@ class SegTrainer(BaseTrainer):
                     if len(config.metrics) > 1 and i != len(config.metrics) - 1:
                         infos = infos[:-1]
                     self.logger.info(infos)
+                one_sided = getattr(self.metrics[i], 'last_one_sided', None)
+                if one_sided is not None and int(one_sided.sum()) > 0:
+                    self.logger.info(f' m{config.metrics[i]}: {int(one_sided.sum())} (image, class) pairs with exactly '
+                                     f'one empty mask scored at the image diagonal (per class {one_sided.tolist()})')
                 if config.use_tb and self.writer is not None and self.cur_epoch < config.total_epoch:
                     self.writer.add_scalar(f'val/m{config.metrics[i]}', scores[i].mean().item(), self.cur_epoch + 1)
                     if config.metrics[i] == 'iou':
@@ -251,9 +263,11 @@ class SegTrainer(BaseTrainer):
         # per-validation record (save_dir/val_history.json, written by BaseTrainer.run): accuracy vs time
         rec = {'epoch': int(self.cur_epoch), 'train_itrs': int(getattr(self, 'train_itrs', 0)),
                'elapsed_s': round(time.perf_counter() - getattr(self, '_t_run', time.perf_counter()), 2),
-               'score': float(score), 'val_best': bool(val_best), 'fp32': bool(getattr(config, 'val_fp32', False))}
+               'val_s': round(time.perf_counter() - t_val, 3),   # this validation: loader, forward, metrics
+               'score': _finite_or_none(float(score)), 'val_best': bool(val_best),
+               'fp32': bool(getattr(config, 'val_fp32', False))}
         for m, v in self.last_scores.items():
-            rec[m] = v.tolist()
+            rec[m] = _finite_or_none(v.tolist())
         self.val_history.append(rec)
         for metric in self.metrics:
             metric.reset()

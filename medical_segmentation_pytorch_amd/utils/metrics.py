@@ -9,8 +9,15 @@ all-reduce of C*C int64, instead of torchmetrics' per-state all_gathers) and der
   * Dice (macro)   = mean over classes present of 2TP / (2TP + FP + FN)   (includes background)
 Dice here ignores no index (the reference constructs ``Dice`` without ``ignore_index``), IoU drops
 ``ignore_index`` pixels; for {0,1} polyp masks both see the same pixels.
+
+Boundary metrics (an addition over the reference): ``HausdorffDistance95``, ``AverageSurfaceDistance`` and
+``SurfaceDice`` score the foreground classes' contours per image (``ops/surface.py`` has the semantics; on
+MI355X the ``surface.hip`` distance-transform kernels).  The three share one :class:`SurfaceAccumulator`, so a
+batch's statistics are computed once however many of them are requested.
 """
 from __future__ import annotations
+
+import weakref
 
 import torch
 import torch.distributed as dist
@@ -108,9 +115,133 @@ def foreground_dice(preds, target, fg=1):
     return torch.where(den > 0, 2 * inter / den.clamp_min(1e-12), torch.ones_like(den)).mean()
 
 
+class SurfaceAccumulator(nn.Module):
+    """Per-class state of the boundary metrics: fp64 sums of the per-image hd95 / assd / nsd, the number of
+    scored (image, class) pairs and the number of those with exactly one empty mask.  Shared by the metric
+    objects built from one config: ``update`` by a metric that has not yet seen the batch the accumulator scored
+    last is a no-op (the tensors are held until the next batch), ``reset`` by any of them zeroes it once."""
+
+    def __init__(self, num_classes, ignore_index=None, nsd_tolerance=2.0):
+        super().__init__()
+        self.num_classes = num_classes
+        self.ignore_index = ignore_index
+        self.nsd_tolerance = float(nsd_tolerance)
+        k = num_classes - 1
+        self.register_buffer('sum', torch.zeros(3, k, dtype=torch.float64))
+        self.register_buffer('count', torch.zeros(k, dtype=torch.long))
+        self.register_buffer('onesided', torch.zeros(k, dtype=torch.long))
+        self._last, self._seen = None, set()
+
+    @torch.no_grad()
+    def update(self, preds, target, owner=None):
+        # the same batch again from another metric of the group (``owner``): same memory, same shape, not written
+        # since.  The tensors are held, so their storage cannot be handed to another batch in between.
+        key = tuple((t.data_ptr(), tuple(t.shape), t.stride(), t.dtype, t._version) for t in (preds, target))
+        if self._last is not None and self._last[0] == key and owner is not None and owner not in self._seen:
+            self._seen.add(owner)
+            return
+        from ..ops.surface import surface_stats
+        dev = self.sum.device
+        surface_stats(preds.to(dev), target.to(dev), self.num_classes, self.ignore_index, self.nsd_tolerance,
+                      {'sum': self.sum, 'count': self.count, 'onesided': self.onesided})
+        self._last, self._seen = (key, preds, target), {owner}
+
+    def reset(self):
+        self.sum.zero_()
+        self.count.zero_()
+        self.onesided.zero_()
+        self._last, self._seen = None, set()
+
+
+class _SurfaceMetric(nn.Module):
+    """Mean over the foreground classes with a scored pair of (sum of per-image values / scored pairs); nan when
+    nothing was scored.  ``compute`` all-reduces the packed state once (SUM over ``group``)."""
+    row = 0
+
+    def __init__(self, num_classes=2, ignore_index=None, nsd_tolerance=2.0, sync=True, group=None, accumulator=None):
+        super().__init__()
+        if num_classes < 2:
+            raise ValueError('surface metrics need num_classes >= 2')
+        self.group = group
+        self.num_classes = num_classes
+        self.sync = sync
+        self.last_one_sided = None     # set by compute(): [C-1] one-sided-empty pairs over all ranks
+        self.acc = accumulator if accumulator is not None else SurfaceAccumulator(num_classes, ignore_index,
+                                                                                  nsd_tolerance)
+        if self.acc.num_classes != num_classes:
+            raise ValueError('shared accumulator was built for another number of classes')
+
+    def update(self, preds, target):
+        self.acc.update(preds, target, owner=id(self))
+
+    def reset(self):
+        self.acc.reset()
+
+    def _synced(self):
+        a = self.acc
+        st = torch.cat([a.sum[self.row:self.row + 1], a.count[None].double(), a.onesided[None].double()])
+        if self.sync and dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            dist.all_reduce(st, group=self.group)
+        return st
+
+    def _per_class(self, st):
+        return torch.where(st[1] > 0, st[0] / st[1].clamp_min(1.0), torch.full_like(st[0], float('nan')))
+
+    def per_class(self):
+        """``[C-1]`` fp32 per foreground class, nan where no pair was scored."""
+        return self._per_class(self._synced()).float()
+
+    def one_sided(self):
+        """``[C-1]`` int64: scored pairs in which exactly one of the two masks was empty (all ranks; a
+        collective like ``compute``, which leaves the same vector in ``last_one_sided``)."""
+        return self._synced()[2].round().long()
+
+    def compute(self):
+        st = self._synced()
+        self.last_one_sided = st[2].round().long()
+        pc = self._per_class(st)
+        scored = st[1] > 0
+        # nanmean without a host sync: nan (0 / 0) when no class was scored
+        return (torch.where(scored, pc, torch.zeros_like(pc)).sum() / scored.sum()).float()
+
+
+class HausdorffDistance95(_SurfaceMetric):
+    """Per-image max of the two directional 95th-percentile boundary distances (MONAI's convention, not
+    medpy's pooled percentile), in pixels; lower is better."""
+    row = 0
+
+
+class AverageSurfaceDistance(_SurfaceMetric):
+    """Average symmetric surface distance in pixels; lower is better."""
+    row = 1
+
+
+class SurfaceDice(_SurfaceMetric):
+    """Normalised surface Dice: the fraction of both boundaries within ``nsd_tolerance`` pixels of the other."""
+    row = 2
+
+
+SURFACE_METRICS = {'hd95': HausdorffDistance95, 'assd': AverageSurfaceDistance, 'nsd': SurfaceDice}
+LOWER_IS_BETTER = ('hd95', 'assd')
+_SURFACE_ACC = weakref.WeakKeyDictionary()     # config object -> the accumulator its surface metrics share
+
+
 def get_seg_metrics(config, metric_name):
     nc = max(config.num_class, 2)          # num_class == 1 (sigmoid) is scored as background/foreground
     group = getattr(config, 'dist_group', None)
+    if metric_name in SURFACE_METRICS:
+        # one accumulator per config: the metrics requested together share a batch's statistics
+        try:
+            acc, store = _SURFACE_ACC.get(config), _SURFACE_ACC.__setitem__
+        except TypeError:      # a config object that cannot be weakly referenced keeps it itself
+            acc, store = getattr(config, '_surface_accumulator', None), \
+                lambda c, a: setattr(c, '_surface_accumulator', a)
+        tol = float(getattr(config, 'nsd_tolerance', 2.0))
+        if acc is None or acc.num_classes != nc or acc.ignore_index != config.ignore_index \
+                or acc.nsd_tolerance != tol:
+            acc = SurfaceAccumulator(nc, config.ignore_index, tol)
+            store(config, acc)
+        return SURFACE_METRICS[metric_name](num_classes=nc, group=group, accumulator=acc)
     if metric_name == 'iou':
         m = JaccardIndex(task='multiclass', num_classes=nc, ignore_index=config.ignore_index, average='none')
     elif metric_name == 'dice':
