@@ -838,6 +838,93 @@ void surface_finalize_t(const at::Tensor& stats, const at::Tensor& sums, const a
                 onesided.data_ptr<int64_t>(), pi, (int)N, (int)K, (int)H, (int)W, cur_stream());
 }
 
+// ---- connected components (components.hip)
+static void cc_planes_check(const at::Tensor& lab, const at::Tensor& root, const at::Tensor& area,
+                            const at::Tensor& aux) {
+  CHECK_U8(lab); CHECK_I32(root); CHECK_I32(area); CHECK_I32(aux);
+  TORCH_CHECK(lab.dim() == 3, "lab must be [B, H, W]");
+  surface_dims_check(lab.size(0), lab.size(1), lab.size(2));
+  TORCH_CHECK(root.numel() == lab.numel() && area.numel() == lab.numel() && aux.numel() == lab.numel(),
+              "root / area / aux must be shaped like lab");
+}
+
+void cc_label_t(const at::Tensor& lab, const at::Tensor& root, const at::Tensor& area, const at::Tensor& aux,
+                const at::Tensor& err, int64_t half, int64_t connectivity, int64_t mode) {
+  cc_planes_check(lab, root, area, aux);
+  CHECK_I32(err);
+  const int64_t B = lab.size(0), H = lab.size(1), W = lab.size(2);
+  const int64_t tiles = ((H + 31) / 32) * ((W + 31) / 32);
+  TORCH_CHECK(B * tiles <= 2147483647LL, "connected components: too many tiles in one call (", B, " images)");
+  TORCH_CHECK(err.numel() == 1 && half >= 0 && half < B, "err must be [1], half in [0, B)");
+  TORCH_CHECK((connectivity == 4 || connectivity == 8) && (mode == 0 || mode == 1),
+              "connectivity must be 4 or 8, mode 0 or 1");
+  cc_label(lab.data_ptr<uint8_t>(), root.data_ptr<int32_t>(), area.data_ptr<int32_t>(), aux.data_ptr<int32_t>(),
+           err.data_ptr<int32_t>(), half, B, (int)H, (int)W, (int)connectivity, (int)mode, cur_stream());
+}
+
+void cc_rank_t(const at::Tensor& root, const at::Tensor& rank, const at::Tensor& num) {
+  CHECK_I32(root); CHECK_I32(rank); CHECK_I64(num);
+  TORCH_CHECK(root.dim() == 3, "root must be [B, H, W]");
+  surface_dims_check(root.size(0), root.size(1), root.size(2));
+  TORCH_CHECK(rank.numel() == root.numel() && num.numel() == root.size(0), "rank like root, num [B]");
+  cc_rank(root.data_ptr<int32_t>(), rank.data_ptr<int32_t>(), num.data_ptr<int64_t>(), root.size(0),
+          root.size(1) * root.size(2), cur_stream());
+}
+
+void cc_gather_t(const at::Tensor& root, const at::Tensor& src, const at::Tensor& out) {
+  CHECK_I32(root); CHECK_I32(src); CHECK_I32(out);
+  TORCH_CHECK(root.dim() == 3, "root must be [B, H, W]");
+  surface_dims_check(root.size(0), root.size(1), root.size(2));
+  TORCH_CHECK(src.numel() == root.numel() && out.numel() == root.numel(), "src / out must be shaped like root");
+  cc_gather(root.data_ptr<int32_t>(), src.data_ptr<int32_t>(), out.data_ptr<int32_t>(), root.size(0),
+            root.size(1) * root.size(2), cur_stream());
+}
+
+void cc_largest_t(const at::Tensor& lab, const at::Tensor& root, const at::Tensor& area, const at::Tensor& key) {
+  cc_planes_check(lab, root, area, area);
+  CHECK_I64(key);
+  TORCH_CHECK(key.numel() == lab.size(0) * kCcKeyCols, "key must be [B, ", kCcKeyCols, "]");
+  cc_largest(lab.data_ptr<uint8_t>(), root.data_ptr<int32_t>(), area.data_ptr<int32_t>(), key.data_ptr<int64_t>(),
+             lab.size(0), lab.size(1) * lab.size(2), cur_stream());
+}
+
+void cc_apply_t(const at::Tensor& lab, const at::Tensor& root, const at::Tensor& area, const at::Tensor& aux,
+                const c10::optional<at::Tensor>& key, const at::Tensor& out, int64_t mode, int64_t min_area) {
+  cc_planes_check(lab, root, area, aux);
+  CHECK_U8(out);
+  TORCH_CHECK(out.numel() == lab.numel() && out.data_ptr() != lab.data_ptr(), "out: shaped like lab, another tensor");
+  TORCH_CHECK((mode == 0 || mode == 1) && min_area >= 0 && min_area <= 2147483647LL, "mode 0 or 1, min_area >= 0");
+  const int64_t* kp = nullptr;
+  if (key.has_value() && key->defined()) {
+    CHECK_I64(*key);
+    TORCH_CHECK(key->numel() == lab.size(0) * kCcKeyCols, "key must be [B, ", kCcKeyCols, "]");
+    kp = key->data_ptr<int64_t>();
+  }
+  cc_apply(lab.data_ptr<uint8_t>(), root.data_ptr<int32_t>(), area.data_ptr<int32_t>(), aux.data_ptr<int32_t>(), kp,
+           out.data_ptr<uint8_t>(), lab.size(0), lab.size(1) * lab.size(2), (int)mode, (int)min_area, cur_stream());
+}
+
+void cc_lesion_t(const at::Tensor& lab, const at::Tensor& root, const at::Tensor& area, const at::Tensor& aux,
+                 const at::Tensor& err, const at::Tensor& state, const at::Tensor& state_err,
+                 const c10::optional<at::Tensor>& per, int64_t K, double min_overlap) {
+  cc_planes_check(lab, root, area, aux);
+  CHECK_I32(err); CHECK_I64(state); CHECK_I64(state_err);
+  const int64_t B = lab.size(0), N = B / 2;
+  TORCH_CHECK(B % 2 == 0 && B <= 65534, "lab must be [2N, H, W] with N <= 32767");
+  TORCH_CHECK(K >= 1 && K < kSurfMaxClasses && state.numel() == 4 * K && err.numel() == 1 && state_err.numel() == 1,
+              "state must be [4, K], err and state_err [1]");
+  TORCH_CHECK(min_overlap >= 0.0 && min_overlap <= 1.0, "min_overlap must be in [0, 1]");
+  int64_t* pp = nullptr;
+  if (per.has_value() && per->defined()) {
+    CHECK_I64(*per);
+    TORCH_CHECK(per->numel() == N * K * 4, "per must be [N, K, 4]");
+    pp = per->data_ptr<int64_t>();
+  }
+  cc_lesion(lab.data_ptr<uint8_t>(), root.data_ptr<int32_t>(), area.data_ptr<int32_t>(), aux.data_ptr<int32_t>(),
+            err.data_ptr<int32_t>(), state.data_ptr<int64_t>(), state_err.data_ptr<int64_t>(), pp, (int)N, (int)K,
+            lab.size(1) * lab.size(2), min_overlap, cur_stream());
+}
+
 
 // ---- decoder-hub ops (decoder.hip)
 void resize_bilinear_t(const at::Tensor& x, const at::Tensor& y, double sh, double sw, bool align, bool accum,
@@ -1348,6 +1435,17 @@ PYBIND11_MODULE(_C, m) {
         py::arg("onesided"), py::arg("per_image"), py::arg("N"), py::arg("K"), py::arg("H"), py::arg("W"));
   m.attr("EDT_MAX_DIM") = kEdtMaxDim;
   m.attr("EDT_NONE") = kEdtNone;
+  m.def("cc_label", &cc_label_t, py::arg("lab"), py::arg("root"), py::arg("area"), py::arg("aux"), py::arg("err"),
+        py::arg("half") = 0, py::arg("connectivity") = 8, py::arg("mode") = 0);
+  m.def("cc_rank", &cc_rank_t);
+  m.def("cc_gather", &cc_gather_t);
+  m.def("cc_largest", &cc_largest_t);
+  m.def("cc_apply", &cc_apply_t, py::arg("lab"), py::arg("root"), py::arg("area"), py::arg("aux"), py::arg("key"),
+        py::arg("out"), py::arg("mode"), py::arg("min_area"));
+  m.def("cc_lesion", &cc_lesion_t, py::arg("lab"), py::arg("root"), py::arg("area"), py::arg("aux"), py::arg("err"),
+        py::arg("state"), py::arg("state_err"), py::arg("per"), py::arg("K"), py::arg("min_overlap"));
+  m.attr("CC_SKIP") = kCcSkip;
+  m.attr("CC_KEY_COLS") = kCcKeyCols;
   m.def("resize_bilinear", &resize_bilinear_t, py::arg("x"), py::arg("y"), py::arg("sh"), py::arg("sw"),
         py::arg("align"), py::arg("accum") = false, py::arg("backward") = false);
   m.def("nc_sums_blocks", &nc_sums_blocks_t);

@@ -290,6 +290,39 @@ void surf_reduce(int32_t* d2, int64_t* stats, double* sums, long B, long HW, int
 void surf_finalize(const int64_t* stats, const double* sums, double* sum, int64_t* count, int64_t* onesided,
                    double* per_image, int N, int K, int H, int W, hipStream_t s);
 
+// components.hip: connected-component labelling of uint8 label planes [B][H][W] (H, W <= kEdtMaxDim), mask clean-up
+// and lesion-wise counters.  A pixel equal to kCcSkip belongs to nothing; any other pixel is connected to a 4- or
+// 8-neighbour holding the same value.
+constexpr int kCcSkip = 255;
+constexpr int kCcKeyCols = 256;        // keep-largest keys per plane, indexed by the label value
+// root [B][HW]: plane-local index y * W + x of the raster-first pixel of the pixel's component, -1 at skipped pixels.
+// area / aux [B][HW], valid at root positions only: the component's pixel count and the sum of a per-pixel weight --
+// mode 0: the pixel lies on the image frame; mode 1: plane (b + half) % B holds the same label at the pixel.
+// err [1]: set to 0, then counts the loops that hit their H*W iteration cap (0 on every correct run).
+void cc_label(const uint8_t* lab, int32_t* root, int32_t* area, int32_t* aux, int32_t* err, long half, long B, int H,
+              int W, int connectivity, int mode, hipStream_t s);
+// rank (at root positions) = 1 + the number of roots before it in raster order; num [B] = roots per plane.
+// One 256-thread block scans a whole plane, 2048 pixels per round: meant for the public `label` on image-sized
+// planes (60 rounds at 352 x 352); a 16384 x 16384 plane is 131072 serial rounds on one CU -- correct but slow, and
+// a batch of fewer planes than CUs leaves the rest of the chip idle.  Neither metric nor clean-up path calls it.
+void cc_rank(const int32_t* root, int32_t* rank, int64_t* num, long B, long HW, hipStream_t s);
+// out[i] = src[root[i]], 0 at skipped pixels
+void cc_gather(const int32_t* root, const int32_t* src, int32_t* out, long B, long HW, hipStream_t s);
+// key [B][kCcKeyCols] = max over the components of label v >= 1 of (area << 32 | ~root); zeroed first
+void cc_largest(const uint8_t* lab, const int32_t* root, const int32_t* area, int64_t* key, long B, long HW,
+                hipStream_t s);
+// mode 0: fill the label-0 components without a frame pixel (aux from cc_label mode 0, connectivity 4) with the label
+// left of their first pixel; mode 1: zero foreground components with area < min_area and, when key is given, all
+// but the class's largest.  out must not alias lab.
+void cc_apply(const uint8_t* lab, const int32_t* root, const int32_t* area, const int32_t* aux, const int64_t* key,
+              uint8_t* out, long B, long HW, int mode, int min_area, hipStream_t s);
+// planes [0, N) the prediction, [N, 2N) the target (cc_label mode 1, half = N): state [4][K] += (GT components, GT
+// hits, predicted components, predicted hits) of classes 1..K, state_err [1] += *err, per (nullable) [N][K][4] +=.
+// A component of area a with i shared pixels is a hit iff i >= 1 and (double)i >= min_overlap * (double)a.
+void cc_lesion(const uint8_t* lab, const int32_t* root, const int32_t* area, const int32_t* aux, const int32_t* err,
+               int64_t* state, int64_t* state_err, int64_t* per, int N, int K, long HW, double min_overlap,
+               hipStream_t s);
+
 // decoder.hip: smp decoder-hub ops (bilinear resize, GroupNorm, adaptive pooling, depthwise conv)
 void resize_bilinear_fwd(const uint16_t* x, uint16_t* y, int N, int IH, int IW, int OH, int OW, int Cp, float sh,
                          float sw, int align, int accum, hipStream_t s);

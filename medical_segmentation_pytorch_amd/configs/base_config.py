@@ -40,6 +40,9 @@ class BaseConfig:
         # Validating
         self.metrics = ['dice']        # the first one drives best-checkpoint selection
         self.nsd_tolerance = 2.0       # pixels: the 'nsd' (surface Dice) metric counts boundary pixels this close
+        self.lesion_min_overlap = 0.0  # 'lesion_*' metrics: a component is a hit when at least this fraction of its
+                                       # area (and at least one pixel) lies in the other mask
+        self.cc_connectivity = 8       # 4 | 8: pixel connectivity of the lesion metrics and the post-processing
         self.val_bs = 16
         self.begin_val_epoch = 0
         self.val_interval = 1
@@ -54,6 +57,10 @@ class BaseConfig:
         self.save_mask = True
         self.blend_prediction = True
         self.blend_alpha = 0.3
+        # mask clean-up of the predicted label map, applied in this order (ops/components.postprocess)
+        self.post_fill_holes = False   # fill background holes enclosed by foreground
+        self.post_min_area = 0         # remove foreground components smaller than this many pixels
+        self.post_keep_largest = False   # keep only the largest component per class
 
         # Loss
         self.loss_type = 'ce'
@@ -173,6 +180,12 @@ class BaseConfig:
         if self.metrics[0] in ('hd95', 'assd'):
             raise ValueError(f"metrics[0] drives best-checkpoint selection as higher-is-better; '{self.metrics[0]}' is "
                              f"a distance (lower is better) -- put 'dice', 'iou' or 'nsd' first")
+        if not 0.0 <= float(self.lesion_min_overlap) <= 1.0:
+            raise ValueError(f'lesion_min_overlap must be in [0, 1], got {self.lesion_min_overlap}')
+        if self.cc_connectivity not in (4, 8):
+            raise ValueError(f'cc_connectivity must be 4 or 8, got {self.cc_connectivity!r}')
+        if int(self.post_min_area) != self.post_min_area or self.post_min_area < 0:
+            raise ValueError(f'post_min_area must be an integer >= 0, got {self.post_min_area!r}')
         auto = getattr(self, '_auto_derived', set())
 
         def derive(name, value, cond):

@@ -41,6 +41,8 @@ def get_parser():
     # Validating
     _flag(p, 'metrics', type=str, nargs='+')
     _flag(p, 'nsd_tolerance', type=float)
+    _flag(p, 'lesion_min_overlap', type=float)
+    _flag(p, 'cc_connectivity', type=int, choices=[4, 8])
     _flag(p, 'val_bs', type=int)
     _flag(p, 'begin_val_epoch', type=int)
     _flag(p, 'val_interval', type=int)
@@ -54,6 +56,9 @@ def get_parser():
     _flag(p, 'save_mask', action='store_false')
     _flag(p, 'blend_prediction', action='store_false')
     _flag(p, 'blend_alpha', type=float)
+    _flag(p, 'post_fill_holes', action='store_true')
+    _flag(p, 'post_min_area', type=int)
+    _flag(p, 'post_keep_largest', action='store_true')
     # Loss
     _flag(p, 'loss_type', type=str, choices=['ce', 'ohem', 'bce', 'dice', 'bce_dice', 'tversky', 'focal', 'ce_dice',
                                              'ce_tversky', 'focal_dice', 'focal_tversky'])

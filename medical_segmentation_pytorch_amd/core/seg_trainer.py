@@ -24,6 +24,7 @@ from PIL import Image
 
 from ..models import get_teacher_model
 from ..ops.bn import flush_pending
+from ..ops.components import postprocess
 from ..runtime.trainer_engine import StepEngine, iteration
 from ..utils import FusedModel, de_parallel, get_colormap, get_seg_metrics, sampler_set_epoch
 from .base_trainer import BaseTrainer
@@ -281,10 +282,27 @@ class SegTrainer(BaseTrainer):
             self.logger.info('\nStart predicting...\n')
         model = de_parallel(self.model).eval()
         fwd = FusedModel(model).eval() if self.fused else model
+        post = dict(fill_holes=bool(getattr(config, 'post_fill_holes', False)),
+                    min_area=int(getattr(config, 'post_min_area', 0)),
+                    keep_largest=bool(getattr(config, 'post_keep_largest', False)))
+        clean = post['fill_holes'] or post['min_area'] > 0 or post['keep_largest']
+        if clean and self.logger:
+            self.logger.info(f'Post-processing the predicted masks: {post}, '
+                             f'connectivity {getattr(config, "cc_connectivity", 8)}\n')
         for images, images_aug, img_names in _tqdm(self.test_loader, config.progress_bar):
             images_aug = images_aug.to(self.device, dtype=torch.float32)
             preds = fwd(images_aug)
-            preds = colorize(preds, self.colormap).cpu().numpy()
+            if clean:
+                # the label map stays on the device: argmax (logit > 0 for a sigmoid head), clean-up, colours
+                labels = (preds[:, 0] > 0) if preds.shape[1] == 1 else preds.argmax(1)
+                labels, errors = postprocess(labels.to(torch.uint8), max(config.num_class, 2), debug=True,
+                                             connectivity=getattr(config, 'cc_connectivity', 8), **post)
+                preds = self.colormap[labels.long()].cpu().numpy()
+                if int(errors) != 0:      # read after the copy above has synchronised anyway
+                    raise RuntimeError(f'post-processing: the labelling kernels reported {int(errors)} loops that '
+                                       f'hit their iteration cap; the masks of {list(img_names)} were not saved')
+            else:
+                preds = colorize(preds, self.colormap).cpu().numpy()
             images = images.cpu().numpy()
             for i in range(preds.shape[0]):
                 save_path = os.path.join(config.save_dir, img_names[i])

@@ -14,6 +14,11 @@ Boundary metrics (an addition over the reference): ``HausdorffDistance95``, ``Av
 ``SurfaceDice`` score the foreground classes' contours per image (``ops/surface.py`` has the semantics; on
 MI355X the ``surface.hip`` distance-transform kernels).  The three share one :class:`SurfaceAccumulator`, so a
 batch's statistics are computed once however many of them are requested.
+
+Lesion-wise metrics (an addition too): ``LesionRecall``, ``LesionPrecision`` and ``LesionF1`` count connected
+components instead of pixels -- how many ground-truth lesions were found and how many predicted blobs were false
+alarms (``ops/components.py`` has the semantics; on MI355X the ``components.hip`` labelling kernels).  They share
+one :class:`LesionAccumulator` in the same way.
 """
 from __future__ import annotations
 
@@ -221,14 +226,153 @@ class SurfaceDice(_SurfaceMetric):
     row = 2
 
 
+class LesionAccumulator(nn.Module):
+    """Per-class state of the lesion-wise metrics: int64 ``counts [4, C-1]`` (GT components, GT hits, predicted
+    components, predicted hits) and the labelling kernels' error counter.  Shared by the metric objects built
+    from one config exactly as :class:`SurfaceAccumulator` is: a batch is scored once however many of them see
+    it, and ``reset`` by any of them zeroes it once."""
+
+    def __init__(self, num_classes, ignore_index=None, min_overlap=0.0, connectivity=8):
+        super().__init__()
+        if not 0.0 <= float(min_overlap) <= 1.0:
+            raise ValueError(f'min_overlap must be in [0, 1], got {min_overlap}')
+        if connectivity not in (4, 8):
+            raise ValueError(f'connectivity must be 4 or 8, got {connectivity!r}')
+        self.num_classes = num_classes
+        self.ignore_index = ignore_index
+        self.min_overlap = float(min_overlap)
+        self.connectivity = int(connectivity)
+        self.register_buffer('counts', torch.zeros(4, num_classes - 1, dtype=torch.long))
+        self.register_buffer('err', torch.zeros(1, dtype=torch.long))
+        self._last, self._seen = None, set()
+
+    @torch.no_grad()
+    def update(self, preds, target, owner=None):
+        key = tuple((t.data_ptr(), tuple(t.shape), t.stride(), t.dtype, t._version) for t in (preds, target))
+        if self._last is not None and self._last[0] == key and owner is not None and owner not in self._seen:
+            self._seen.add(owner)
+            return
+        from ..ops.components import lesion_stats
+        dev = self.counts.device
+        lesion_stats(preds.to(dev), target.to(dev), self.num_classes, self.ignore_index, self.min_overlap,
+                     self.connectivity, {'counts': self.counts, 'err': self.err})
+        self._last, self._seen = (key, preds, target), {owner}
+
+    def reset(self):
+        self.counts.zero_()
+        self.err.zero_()
+        self._last, self._seen = None, set()
+
+
+class _LesionMetric(nn.Module):
+    """Mean over the scored foreground classes of a ratio of component counts (``ops/components.py`` has the
+    semantics); nan when no class is scored or the kernels reported an error.  ``compute`` all-reduces the packed
+    int64 state once (SUM over ``group``)."""
+
+    def __init__(self, num_classes=2, ignore_index=None, min_overlap=0.0, connectivity=8, sync=True, group=None,
+                 accumulator=None):
+        super().__init__()
+        if num_classes < 2:
+            raise ValueError('lesion metrics need num_classes >= 2')
+        self.group = group
+        self.num_classes = num_classes
+        self.sync = sync
+        self.acc = accumulator if accumulator is not None else LesionAccumulator(num_classes, ignore_index,
+                                                                                 min_overlap, connectivity)
+        if self.acc.num_classes != num_classes:
+            raise ValueError('shared accumulator was built for another number of classes')
+
+    def update(self, preds, target):
+        self.acc.update(preds, target, owner=id(self))
+
+    def reset(self):
+        self.acc.reset()
+
+    def _synced(self):
+        st = torch.cat([self.acc.counts.reshape(-1), self.acc.err])
+        if self.sync and dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            dist.all_reduce(st, group=self.group)
+        return st[:-1].view(4, -1).double(), st[-1]
+
+    @staticmethod
+    def _ratio(hits, comps):
+        return torch.where(comps > 0, hits / comps.clamp_min(1.0), torch.zeros_like(hits))
+
+    def _values(self, c):
+        """``c [4, C-1]`` fp64 -> (per-class value, per-class scored flag)"""
+        raise NotImplementedError
+
+    def counts(self):
+        """``[4, C-1]`` int64 over all ranks (a collective like ``compute``): GT components, GT hits, predicted
+        components, predicted hits."""
+        return self._synced()[0].round().long()
+
+    def per_class(self):
+        """``[C-1]`` fp32 per foreground class, nan where the class is not scored."""
+        c, err = self._synced()
+        v, scored = self._values(c)
+        return torch.where(scored & (err == 0), v, torch.full_like(v, float('nan'))).float()
+
+    def compute(self):
+        c, err = self._synced()
+        v, scored = self._values(c)
+        # nanmean without a host sync: nan (0 / 0) when no class was scored
+        mean = torch.where(scored, v, torch.zeros_like(v)).sum() / scored.sum()
+        return torch.where(err == 0, mean, torch.full_like(mean, float('nan'))).float()
+
+
+class LesionRecall(_LesionMetric):
+    """Found ground-truth components / ground-truth components; a class is scored iff it has ground-truth ones."""
+
+    def _values(self, c):
+        return self._ratio(c[1], c[0]), c[0] > 0
+
+
+class LesionPrecision(_LesionMetric):
+    """Predicted components that hit the ground truth / predicted components; scored iff the class has predicted
+    ones."""
+
+    def _values(self, c):
+        return self._ratio(c[3], c[2]), c[2] > 0
+
+
+class LesionF1(_LesionMetric):
+    """2PR / (P + R) per class, a side without components counting 0; scored iff the class has components on either
+    side."""
+
+    def _values(self, c):
+        r, p = self._ratio(c[1], c[0]), self._ratio(c[3], c[2])
+        f1 = torch.where(p + r > 0, 2 * p * r / (p + r).clamp_min(1e-300), torch.zeros_like(p))
+        return f1, (c[0] > 0) | (c[2] > 0)
+
+
 SURFACE_METRICS = {'hd95': HausdorffDistance95, 'assd': AverageSurfaceDistance, 'nsd': SurfaceDice}
+LESION_METRICS = {'lesion_recall': LesionRecall, 'lesion_precision': LesionPrecision, 'lesion_f1': LesionF1}
 LOWER_IS_BETTER = ('hd95', 'assd')
 _SURFACE_ACC = weakref.WeakKeyDictionary()     # config object -> the accumulator its surface metrics share
+_LESION_ACC = weakref.WeakKeyDictionary()      # config object -> the accumulator its lesion metrics share
+
+
+def _lesion_metric(config, metric_name, nc, group):
+    try:
+        acc, store = _LESION_ACC.get(config), _LESION_ACC.__setitem__
+    except TypeError:      # a config object that cannot be weakly referenced keeps it itself
+        acc, store = getattr(config, '_lesion_accumulator', None), \
+            lambda c, a: setattr(c, '_lesion_accumulator', a)
+    ov = float(getattr(config, 'lesion_min_overlap', 0.0))
+    conn = int(getattr(config, 'cc_connectivity', 8))
+    if acc is None or acc.num_classes != nc or acc.ignore_index != config.ignore_index \
+            or acc.min_overlap != ov or acc.connectivity != conn:
+        acc = LesionAccumulator(nc, config.ignore_index, ov, conn)
+        store(config, acc)
+    return LESION_METRICS[metric_name](num_classes=nc, group=group, accumulator=acc)
 
 
 def get_seg_metrics(config, metric_name):
     nc = max(config.num_class, 2)          # num_class == 1 (sigmoid) is scored as background/foreground
     group = getattr(config, 'dist_group', None)
+    if metric_name in LESION_METRICS:
+        return _lesion_metric(config, metric_name, nc, group)
     if metric_name in SURFACE_METRICS:
         # one accumulator per config: the metrics requested together share a batch's statistics
         try:

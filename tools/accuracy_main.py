@@ -31,8 +31,9 @@ def summarise(hist, target):
         j = r['iou'][-1] if 'iou' in r else None
         return None if j is None else round(2 * j / (1 + j), 4)
 
-    def surface(r):   # boundary metrics, when the run validated them (--extra --metrics dice iou hd95 nsd)
-        return {k: (None if r[k] is None else round(r[k], 4)) for k in ('hd95', 'assd', 'nsd') if k in r}
+    def extra_metrics(r):   # boundary / lesion-wise metrics, when the run validated them (--extra --metrics dice iou hd95 nsd)
+        names = ('hd95', 'assd', 'nsd', 'lesion_recall', 'lesion_precision', 'lesion_f1')
+        return {k: (None if r[k] is None else round(r[k], 4)) for k in names if k in r}
 
     hit = next((r for r in rows if r['score'] >= target), None)
     return {
@@ -40,12 +41,12 @@ def summarise(hist, target):
         'best': None if best is None else {'epoch': best['epoch'], 'train_itrs': best['train_itrs'],
                                            'elapsed_s': best['elapsed_s'], 'macro_dice': round(best['score'], 4),
                                            'fg_dice': fg(best), 'miou': round(sum(best['iou']) / len(best['iou']), 4)
-                                           if 'iou' in best else None, **surface(best)},
+                                           if 'iou' in best else None, **extra_metrics(best)},
         # val_best runs on the val split, then (MyConfig use_test_set) on the held-out test split
         **{name: None if len(final) <= i else {'macro_dice': round(final[i]['score'], 4), 'fg_dice': fg(final[i]),
                                                 'miou': round(sum(final[i]['iou']) / len(final[i]['iou']), 4)
                                                 if 'iou' in final[i] else None, 'fp32': final[i]['fp32'],
-                                                **surface(final[i])}
+                                                **extra_metrics(final[i])}
            for i, name in enumerate(('val_best', 'test_best'))},
         f'time_to_macro_dice_{target}': None if hit is None else {'elapsed_s': hit['elapsed_s'],
                                                                   'train_itrs': hit['train_itrs'],
@@ -53,7 +54,7 @@ def summarise(hist, target):
         'wall_s': h['wall_s'], 'val_s_total': round(sum(r.get('val_s', 0.0) for r in h['history']), 2),
         'validations': len(h['history']), 'iters_per_epoch': h['iters_per_epoch'], 'train_bs': h['train_bs'],
         'history': [{'epoch': r['epoch'], 'itrs': r['train_itrs'], 's': r['elapsed_s'], 'dice': round(r['score'], 4),
-                     'fg_dice': fg(r), **surface(r)} for r in rows],
+                     'fg_dice': fg(r), **extra_metrics(r)} for r in rows],
     }
 
 
