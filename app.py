@@ -76,9 +76,15 @@ class PerformanceTracker:
 
 class PolyPredictorApp:
     def __init__(self, model_path=None, model='smp', encoder='resnet50', decoder='unet', base_channel=None,
-                 size=320, colormap_path=None, device=None):
+                 size=320, colormap_path=None, device=None, inference=None):
+        """``inference``: sliding-window / flip-TTA fields of the config (``infer_window``, ``infer_overlap``,
+        ``infer_blend``, ``infer_sigma_scale``, ``infer_batch``, ``tta_flips``, ``tta_average``); unset: one
+        whole-image forward."""
         self.config = MyConfig()
         self.config.is_testing = True
+        self.tiled = self.config.set_inference(**(inference or {}))
+        if self.tiled is not None:
+            print(f'[app] sliding-window inference / flip TTA: {self.tiled}', file=sys.stderr)
         self.performance_tracker = PerformanceTracker()
         self.config.model, self.config.encoder, self.config.decoder = model, encoder, decoder
         self.config.encoder_weights = None
@@ -130,7 +136,12 @@ class PolyPredictorApp:
     @torch.no_grad()
     def predict(self, input_tensor):
         t0 = time.time()
-        pred = self.forward(input_tensor)
+        if self.tiled is None:
+            pred = self.forward(input_tensor)
+        else:
+            from medical_segmentation_pytorch_amd.ops.tiled import sliding_window_inference
+            pred = sliding_window_inference(input_tensor, lambda x: self.forward(x).float(),
+                                            **{**self.tiled, 'window': self.tiled['window'] or input_tensor.shape[2:]})
         if self.device.type == 'cuda':
             torch.cuda.synchronize()
         self.performance_tracker.add_inference_time(time.time() - t0)
@@ -229,8 +240,18 @@ def main(argv=None):
     ap.add_argument('--out', default='app_out')
     ap.add_argument('--serve', action='store_true')
     ap.add_argument('--port', type=int, default=8000)
+    ap.add_argument('--infer-window', type=int, nargs='+', default=None, help='sliding-window size: w, or h w')
+    ap.add_argument('--infer-overlap', type=float, default=None)
+    ap.add_argument('--infer-blend', choices=['gaussian', 'constant'], default=None)
+    ap.add_argument('--infer-sigma-scale', type=float, default=None)
+    ap.add_argument('--infer-batch', type=int, default=None)
+    ap.add_argument('--tta-flips', choices=['', 'h', 'v', 'hv'], default=None)
+    ap.add_argument('--tta-average', choices=['logits', 'probs'], default=None)
     a = ap.parse_args(argv)
-    app = PolyPredictorApp(a.model_path, a.model, a.encoder, a.decoder, a.base_channel)
+    inference = {'infer_window': a.infer_window, 'infer_overlap': a.infer_overlap, 'infer_blend': a.infer_blend,
+                 'infer_sigma_scale': a.infer_sigma_scale, 'infer_batch': a.infer_batch, 'tta_flips': a.tta_flips,
+                 'tta_average': a.tta_average}
+    app = PolyPredictorApp(a.model_path, a.model, a.encoder, a.decoder, a.base_channel, inference=inference)
     if a.serve:
         import uvicorn
         uvicorn.run(make_server(app), host='127.0.0.1', port=a.port)

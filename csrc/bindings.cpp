@@ -925,6 +925,71 @@ void cc_lesion_t(const at::Tensor& lab, const at::Tensor& root, const at::Tensor
             lab.size(1) * lab.size(2), min_overlap, cur_stream());
 }
 
+// ---- sliding-window inference (tiled.hip)
+static int64_t tile_views(int64_t flips) {
+  TORCH_CHECK(flips >= 0 && flips <= 3, "flips must be 0 (''), 1 ('h'), 2 ('v') or 3 ('hv')");
+  return flips == 0 ? 1 : (flips == 3 ? 4 : 2);
+}
+
+// the window grid against the image: every window lies inside the padded frame and the padding is that of an image
+// smaller than the window
+static void tile_geometry_check(int64_t H, int64_t W, int64_t wh, int64_t ww, int64_t ny, int64_t nx, int64_t py,
+                                int64_t px, const at::Tensor& starts) {
+  constexpr int64_t kMax = 1 << 20;
+  TORCH_CHECK(H >= 1 && W >= 1 && wh >= 1 && ww >= 1 && H <= kMax && W <= kMax && wh <= kMax && ww <= kMax,
+              "sliding window: image and window extents must be in [1, ", kMax, "]");
+  TORCH_CHECK(ny >= 1 && nx >= 1 && ny <= H && nx <= W, "sliding window: ny / nx must be in [1, H] / [1, W]");
+  TORCH_CHECK(py == std::max<int64_t>(0, wh - H) / 2 && px == std::max<int64_t>(0, ww - W) / 2,
+              "sliding window: the padding must be (max(0, w - L)) / 2 per axis");
+  CHECK_I32(starts);
+  TORCH_CHECK(starts.numel() == ny + nx, "starts must be int32 [ny + nx]");
+}
+
+void window_gather_t(const at::Tensor& img, const at::Tensor& out, const at::Tensor& starts, int64_t ny, int64_t nx,
+                     int64_t py, int64_t px, int64_t flips, int64_t m0) {
+  CHECK_F32(img); CHECK_F32(out);
+  TORCH_CHECK(img.dim() == 4 && out.dim() == 4 && img.size(1) == out.size(1) && img.numel() > 0 && out.numel() > 0,
+              "img must be [N, Cin, H, W] and out [B, Cin, wh, ww]");
+  tile_views(flips);
+  tile_geometry_check(img.size(2), img.size(3), out.size(2), out.size(3), ny, nx, py, px, starts);
+  TORCH_CHECK(m0 >= 0, "m0 must be >= 0");
+  window_gather(f32(img), f32(out), starts.data_ptr<int32_t>(), (int)img.size(0), (int)img.size(1), (int)img.size(2),
+                (int)img.size(3), (int)out.size(2), (int)out.size(3), (int)ny, (int)nx, (int)py, (int)px, (int)flips,
+                m0, out.size(0), cur_stream());
+}
+
+void window_blend_accumulate_t(const at::Tensor& logits, const at::Tensor& acc, const at::Tensor& starts,
+                               const at::Tensor& cover, const at::Tensor& wy, const at::Tensor& wx, int64_t ny,
+                               int64_t nx, int64_t py, int64_t px, int64_t flips, int64_t m0, bool probs, int64_t n0,
+                               int64_t n1, int64_t y0, int64_t y1) {
+  CHECK_F32(logits); CHECK_F32(acc); CHECK_F32(wy); CHECK_F32(wx); CHECK_I32(cover);
+  TORCH_CHECK(logits.dim() == 4 && acc.dim() == 4 && logits.size(1) == acc.size(1) && logits.numel() > 0 &&
+              acc.numel() > 0, "logits must be [B, C, wh, ww] and acc [N, C, H, W]");
+  const int64_t N = acc.size(0), C = acc.size(1), H = acc.size(2), W = acc.size(3);
+  const int64_t wh = logits.size(2), ww = logits.size(3);
+  TORCH_CHECK(C <= kTileMaxClasses, "sliding window: at most ", kTileMaxClasses, " classes");
+  tile_views(flips);
+  tile_geometry_check(H, W, wh, ww, ny, nx, py, px, starts);
+  TORCH_CHECK(cover.numel() == 2 * H + 2 * W && wy.numel() == wh && wx.numel() == ww,
+              "cover must be int32 [2H + 2W], wy [wh], wx [ww]");
+  TORCH_CHECK(m0 >= 0 && 0 <= n0 && n0 <= n1 && n1 <= N && 0 <= y0 && y0 <= y1 && y1 <= H,
+              "m0 >= 0, images [n0, n1) within [0, N) and rows [y0, y1) within [0, H)");
+  window_blend_accumulate(f32(logits), f32(acc), starts.data_ptr<int32_t>(), cover.data_ptr<int32_t>(), f32(wy),
+                          f32(wx), (int)N, (int)C, (int)H, (int)W, (int)wh, (int)ww, (int)ny, (int)nx, (int)py,
+                          (int)px, (int)flips, m0, logits.size(0), probs, (int)n0, (int)n1, (int)y0, (int)y1,
+                          cur_stream());
+}
+
+void window_blend_finalize_t(const at::Tensor& acc, const at::Tensor& ysum, const at::Tensor& xsum, int64_t V,
+                             bool probs) {
+  CHECK_F32(acc); CHECK_F32(ysum); CHECK_F32(xsum);
+  TORCH_CHECK(acc.dim() == 4 && acc.numel() > 0, "acc must be [N, C, H, W]");
+  TORCH_CHECK(ysum.numel() == acc.size(2) && xsum.numel() == acc.size(3), "ysum must be [H], xsum [W]");
+  TORCH_CHECK(V == 1 || V == 2 || V == 4, "V must be 1, 2 or 4");
+  window_blend_finalize(f32(acc), f32(ysum), f32(xsum), (int)acc.size(0), (int)acc.size(1), (int)acc.size(2),
+                        (int)acc.size(3), (int)V, probs, cur_stream());
+}
+
 
 // ---- decoder-hub ops (decoder.hip)
 void resize_bilinear_t(const at::Tensor& x, const at::Tensor& y, double sh, double sw, bool align, bool accum,
@@ -1446,6 +1511,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("state"), py::arg("state_err"), py::arg("per"), py::arg("K"), py::arg("min_overlap"));
   m.attr("CC_SKIP") = kCcSkip;
   m.attr("CC_KEY_COLS") = kCcKeyCols;
+  m.def("window_gather", &window_gather_t);
+  m.def("window_blend_accumulate", &window_blend_accumulate_t);
+  m.def("window_blend_finalize", &window_blend_finalize_t);
+  m.attr("TILE_MAX_CLASSES") = kTileMaxClasses;
   m.def("resize_bilinear", &resize_bilinear_t, py::arg("x"), py::arg("y"), py::arg("sh"), py::arg("sw"),
         py::arg("align"), py::arg("accum") = false, py::arg("backward") = false);
   m.def("nc_sums_blocks", &nc_sums_blocks_t);

@@ -323,6 +323,26 @@ void cc_lesion(const uint8_t* lab, const int32_t* root, const int32_t* area, con
                int64_t* state, int64_t* state_err, int64_t* per, int N, int K, long HW, double min_overlap,
                hipStream_t s);
 
+// tiled.hip: sliding-window inference with flip test-time augmentation.  Window m = ((n * ny + iy) * nx + ix) * V + v
+// starts at (starts[iy], starts[ny + ix]) of the frame padded by (py, px) before the image; flips 0 '', 1 'h', 2 'v',
+// 3 'hv' (V = 1, 2, 2, 4 views: identity, h, v, h.v in that order).  All tensors fp32 NCHW.
+constexpr int kTileMaxClasses = 64;
+// out [B][Cin][wh][ww] = windows [m0, m0 + B) of img [N][Cin][H][W], zero outside the image and past the last window
+void window_gather(const float* img, float* out, const int* starts, int N, int Cin, int H, int W, int wh, int ww,
+                   int ny, int nx, int py, int px, int flips, long m0, long B, hipStream_t s);
+// acc [N][C][H][W] += wy[ky] * wx[kx] * f(logits [B][C][wh][ww]) over the windows [m0, m0 + B) covering each pixel, in
+// ascending m (one thread per pixel, no atomics); f = identity, or (probs) softmax over C / sigmoid for C == 1.
+// cover [2H + 2W]: first / last covering window index per image row, then per image column.  Only images [n0, n1) and
+// rows [y0, y1) are visited (they must contain every pixel the chunk's windows touch).
+void window_blend_accumulate(const float* logits, float* acc, const int* starts, const int* cover, const float* wy,
+                             const float* wx, int N, int C, int H, int W, int wh, int ww, int ny, int nx, int py,
+                             int px, int flips, long m0, long B, bool probs, int n0, int n1, int y0, int y1,
+                             hipStream_t s);
+// in place: acc / (ysum[y] * xsum[x] * V); probs: log(max(p, FLT_MIN)), or for C == 1 the logit of p clamped to
+// [FLT_MIN, 1 - 2^-24]
+void window_blend_finalize(float* acc, const float* ysum, const float* xsum, int N, int C, int H, int W, int V,
+                           bool probs, hipStream_t s);
+
 // decoder.hip: smp decoder-hub ops (bilinear resize, GroupNorm, adaptive pooling, depthwise conv)
 void resize_bilinear_fwd(const uint16_t* x, uint16_t* y, int N, int IH, int IW, int OH, int OW, int Cp, float sh,
                          float sw, int align, int accum, hipStream_t s);

@@ -48,6 +48,17 @@ class BaseConfig:
         self.val_interval = 1
         self.val_img_stride = 1
 
+        # Inference (validate, predict, app): sliding windows and flip test-time augmentation (ops/tiled.py; absent
+        # from the reference).  Both unset: one whole-image forward, exactly as before.
+        self.infer_window = None       # None | w | (h, w): run the network on windows of this size at native
+                                       # resolution (a positive multiple of val_img_stride)
+        self.infer_overlap = 0.5       # fraction of a window shared with its neighbour, in [0, 0.75]
+        self.infer_blend = 'gaussian'  # 'gaussian' | 'constant' importance map of the overlap blend
+        self.infer_sigma_scale = 0.125   # gaussian sigma as a fraction of the window extent
+        self.infer_batch = 16          # windows (views included) per forward
+        self.tta_flips = ''            # '' | 'h' | 'v' | 'hv': mirrored views averaged with the identity
+        self.tta_average = 'logits'    # 'logits' | 'probs': what the windows and views average
+
         # Testing
         self.is_testing = False
         self.test_bs = 16
@@ -186,6 +197,7 @@ class BaseConfig:
             raise ValueError(f'cc_connectivity must be 4 or 8, got {self.cc_connectivity!r}')
         if int(self.post_min_area) != self.post_min_area or self.post_min_area < 0:
             raise ValueError(f'post_min_area must be an integer >= 0, got {self.post_min_area!r}')
+        self.check_inference()
         auto = getattr(self, '_auto_derived', set())
 
         def derive(name, value, cond):
@@ -209,6 +221,54 @@ class BaseConfig:
             self.num_channel = 3 if self.num_channel is None else self.num_channel
         self._auto_derived = auto
         return self
+
+    INFERENCE_FIELDS = ('infer_window', 'infer_overlap', 'infer_blend', 'infer_sigma_scale', 'infer_batch',
+                        'tta_flips', 'tta_average')
+
+    def set_inference(self, **fields):
+        """Set sliding-window / TTA fields by name (``None`` keeps the current value), validate them and return
+        :meth:`inference_settings` -- for callers that do not go through the parser (``app.py``)."""
+        for k, v in fields.items():
+            if k not in self.INFERENCE_FIELDS:
+                raise ValueError(f'unknown inference option {k!r} (one of {self.INFERENCE_FIELDS})')
+            if v is not None:
+                setattr(self, k, v)
+        self.check_inference()
+        return self.inference_settings()
+
+    def check_inference(self):
+        """Validate the sliding-window / TTA fields; ``infer_window`` is normalised to ``None`` or ``(h, w)``."""
+        if not 0.0 <= float(self.infer_overlap) <= 0.75:
+            raise ValueError(f'infer_overlap must be in [0, 0.75], got {self.infer_overlap!r}')
+        if self.infer_blend not in ('gaussian', 'constant'):
+            raise ValueError(f"infer_blend must be 'gaussian' or 'constant', got {self.infer_blend!r}")
+        if self.tta_flips not in ('', 'h', 'v', 'hv'):
+            raise ValueError(f"tta_flips must be '', 'h', 'v' or 'hv', got {self.tta_flips!r}")
+        if self.tta_average not in ('logits', 'probs'):
+            raise ValueError(f"tta_average must be 'logits' or 'probs', got {self.tta_average!r}")
+        if not float(self.infer_sigma_scale) > 0:
+            raise ValueError(f'infer_sigma_scale must be > 0, got {self.infer_sigma_scale!r}')
+        if int(self.infer_batch) != self.infer_batch or self.infer_batch < 1:
+            raise ValueError(f'infer_batch must be an integer >= 1, got {self.infer_batch!r}')
+        win = self.infer_window
+        if win is not None:
+            win = list(win) if isinstance(win, (tuple, list)) else [win]
+            if len(win) == 1:
+                win = win * 2
+            stride = max(1, int(self.val_img_stride))
+            if len(win) != 2 or any(int(v) != v or v < 1 or v % stride for v in win):
+                raise ValueError(f'infer_window must be one or two positive multiples of val_img_stride ({stride}), '
+                                 f'got {self.infer_window!r}')
+            self.infer_window = (int(win[0]), int(win[1]))
+
+    def inference_settings(self):
+        """``None`` when neither sliding windows nor flip TTA are asked for, else the keyword arguments of
+        ``ops.tiled.sliding_window_inference`` (``window`` None: the caller takes the whole image)."""
+        if self.infer_window is None and not self.tta_flips:
+            return None
+        return {'window': self.infer_window, 'overlap': float(self.infer_overlap), 'blend': self.infer_blend,
+                'sigma_scale': float(self.infer_sigma_scale), 'flips': self.tta_flips, 'average': self.tta_average,
+                'batch': int(self.infer_batch)}
 
     def to_dict(self):
         return {k: v for k, v in vars(self).items() if not k.startswith('_')}

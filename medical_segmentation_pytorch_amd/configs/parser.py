@@ -47,6 +47,14 @@ def get_parser():
     _flag(p, 'begin_val_epoch', type=int)
     _flag(p, 'val_interval', type=int)
     _flag(p, 'val_img_stride', type=int)
+    # Inference: sliding windows and flip test-time augmentation
+    _flag(p, 'infer_window', type=int, nargs='+')
+    _flag(p, 'infer_overlap', type=float)
+    _flag(p, 'infer_blend', type=str, choices=['gaussian', 'constant'])
+    _flag(p, 'infer_sigma_scale', type=float)
+    _flag(p, 'infer_batch', type=int)
+    _flag(p, 'tta_flips', type=str, choices=['', 'h', 'v', 'hv'])
+    _flag(p, 'tta_average', type=str, choices=['logits', 'probs'])
     # Testing
     _flag(p, 'is_testing', action='store_true')
     _flag(p, 'test_bs', type=int)

@@ -208,7 +208,8 @@ class BaseTrainer:
                 if rng is not None:
                     torch.set_rng_state(rng['torch'].cpu())
                     keys, pos, has_gauss, gauss = rng['numpy']
-                    np.random.set_state(('MT19937', keys.numpy().astype(np.uint32), pos, has_gauss, gauss))
+                    # (the checkpoint is mapped to self.device: the numpy keys come back as a device tensor)
+                    np.random.set_state(('MT19937', keys.cpu().numpy().astype(np.uint32), pos, has_gauss, gauss))
                     random.setstate((rng['python'][1], tuple(rng['python'][0]), None))
                 if self.main_rank and self.logger:
                     self.logger.info(f'Resume training from {config.load_ckpt_path}')

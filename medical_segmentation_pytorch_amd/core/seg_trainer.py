@@ -29,6 +29,7 @@ from ..runtime.trainer_engine import StepEngine, iteration
 from ..utils import FusedModel, de_parallel, get_colormap, get_seg_metrics, sampler_set_epoch
 from .base_trainer import BaseTrainer
 from ..ops.resample import colorize, resize_bilinear
+from ..ops.tiled import sliding_window_inference
 from ..utils.tracing import trace_range
 from ..utils.watchdog import check_finite
 from .loss import kd_loss_fn
@@ -217,21 +218,33 @@ class SegTrainer(BaseTrainer):
             self._ema_exec = (ema, ex)
         return ex(images)
 
+    def _log_inference(self, tiled):
+        if tiled is not None and self.logger and self.main_rank and not getattr(self, '_inference_logged', False):
+            self._inference_logged = True
+            self.logger.info(f'Sliding-window inference / flip TTA: {tiled} (window None: the whole image)\n')
+
     @torch.no_grad()
     def validate(self, config, loader, val_best=False):
         self.config_ref = config
         t_val = time.perf_counter()
         pbar = _tqdm(loader, self.main_rank and config.progress_bar)
+        tiled = config.inference_settings()
+        self._log_inference(tiled)
         for images, masks in pbar:
             images = images.to(self.device, dtype=torch.float32)
             _, _, H, W = images.shape
             stride = config.val_img_stride
-            resized = H % stride != 0 or W % stride != 0
+            # windows run at native resolution; flip TTA alone keeps the stride-aligned whole image as its one window
+            resized = (H % stride != 0 or W % stride != 0) and (tiled is None or tiled['window'] is None)
             if resized:
                 images = resize_bilinear(images, (H // stride * stride, W // stride * stride))
             masks = masks.to(self.device, dtype=torch.long)
             with trace_range('val/forward'):
-                preds = self._ema_forward(images)
+                if tiled is None:
+                    preds = self._ema_forward(images)
+                else:
+                    preds = sliding_window_inference(images, self._ema_forward,
+                                                     **{**tiled, 'window': tiled['window'] or images.shape[2:]})
             if resized:
                 preds = resize_bilinear(preds, masks.size()[1:], align_corners=True)
             if preds.shape[1] == 1:   # binary (sigmoid) path -> two-class logits for the confmat
@@ -267,6 +280,8 @@ class SegTrainer(BaseTrainer):
                'val_s': round(time.perf_counter() - t_val, 3),   # this validation: loader, forward, metrics
                'score': _finite_or_none(float(score)), 'val_best': bool(val_best),
                'fp32': bool(getattr(config, 'val_fp32', False))}
+        if tiled is not None:
+            rec['inference'] = {k: (list(v) if isinstance(v, tuple) else v) for k, v in tiled.items()}
         for m, v in self.last_scores.items():
             rec[m] = _finite_or_none(v.tolist())
         self.val_history.append(rec)
@@ -289,9 +304,15 @@ class SegTrainer(BaseTrainer):
         if clean and self.logger:
             self.logger.info(f'Post-processing the predicted masks: {post}, '
                              f'connectivity {getattr(config, "cc_connectivity", 8)}\n')
+        tiled = config.inference_settings()
+        self._log_inference(tiled)
         for images, images_aug, img_names in _tqdm(self.test_loader, config.progress_bar):
             images_aug = images_aug.to(self.device, dtype=torch.float32)
-            preds = fwd(images_aug)
+            if tiled is None:
+                preds = fwd(images_aug)
+            else:
+                preds = sliding_window_inference(images_aug, lambda x: fwd(x).float(),
+                                                 **{**tiled, 'window': tiled['window'] or images_aug.shape[2:]})
             if clean:
                 # the label map stays on the device: argmax (logit > 0 for a sigmoid head), clean-up, colours
                 labels = (preds[:, 0] > 0) if preds.shape[1] == 1 else preds.argmax(1)

@@ -33,7 +33,10 @@ def summarise(hist, target):
 
     def extra_metrics(r):   # boundary / lesion-wise metrics, when the run validated them (--extra --metrics dice iou hd95 nsd)
         names = ('hd95', 'assd', 'nsd', 'lesion_recall', 'lesion_precision', 'lesion_f1')
-        return {k: (None if r[k] is None else round(r[k], 4)) for k in names if k in r}
+        out = {k: (None if r[k] is None else round(r[k], 4)) for k in names if k in r}
+        if 'inference' in r:    # sliding-window / flip-TTA settings of the validation (--extra --infer_window 352 ...)
+            out['inference'] = r['inference']
+        return out
 
     hit = next((r for r in rows if r['score'] >= target), None)
     return {
@@ -46,6 +49,7 @@ def summarise(hist, target):
         **{name: None if len(final) <= i else {'macro_dice': round(final[i]['score'], 4), 'fg_dice': fg(final[i]),
                                                 'miou': round(sum(final[i]['iou']) / len(final[i]['iou']), 4)
                                                 if 'iou' in final[i] else None, 'fp32': final[i]['fp32'],
+                                                'val_s': final[i].get('val_s'),
                                                 **extra_metrics(final[i])}
            for i, name in enumerate(('val_best', 'test_best'))},
         f'time_to_macro_dice_{target}': None if hit is None else {'elapsed_s': hit['elapsed_s'],
@@ -77,6 +81,9 @@ def main():
     ap.add_argument('--target', type=float, default=0.98)
     ap.add_argument('--save-dir', default='')
     ap.add_argument('--out', default='')
+    ap.add_argument('--eval-only', action='store_true',
+                    help='resume from --save-dir/last.pth of a finished run with the same --epochs: no training, only '
+                         'val_best on its best.pth (e.g. under other --extra inference settings)')
     ap.add_argument('--extra', nargs=argparse.REMAINDER, default=[])
     a = ap.parse_args()
     save = a.save_dir or tempfile.mkdtemp(prefix='msp_acc_')
@@ -85,8 +92,11 @@ def main():
            '--synthetic_num', str(a.train_images), str(a.val_images), str(a.val_images), '--train_bs', str(a.batch),
            '--total_epoch', str(a.epochs), '--val_interval', str(a.val_every), '--begin_val_epoch', str(a.begin_val),
            '--lr_scale', a.lr_scale, '--accum_steps', str(a.accum),
-           '--val_bs', '16', '--save_dir', save, '--base_lr', str(a.base_lr), '--use_tb', '--load_ckpt',
-           '--no_progress_bar', '--log_interval', '1000'] + (['--val_fp32'] if a.val_fp32 else []) + a.extra
+           '--val_bs', '16', '--save_dir', save, '--base_lr', str(a.base_lr), '--use_tb',
+           '--no_progress_bar', '--log_interval', '1000'] + (['--val_fp32'] if a.val_fp32 else []) \
+        + ([] if a.eval_only else ['--load_ckpt']) + a.extra   # (--load_ckpt is store_false: train from scratch)
+    if a.eval_only and not (a.save_dir and os.path.isfile(os.path.join(a.save_dir, 'last.pth'))):
+        sys.exit('accuracy_main: --eval-only needs --save-dir with the last.pth / best.pth of a finished run')
     print('[acc]', ' '.join(cmd), file=sys.stderr, flush=True)
     t0 = time.time()
     r = subprocess.run(cmd, cwd=ROOT)
@@ -96,7 +106,7 @@ def main():
            'batch': a.batch, 'accum_steps': a.accum, 'global_batch': a.batch * a.accum, 'epochs': a.epochs, 'size': a.size, 'train_images': a.train_images,
            'val_images': a.val_images, 'lr_scale': a.lr_scale,
            'adam_lr': json.load(open(os.path.join(save, 'config.json'))).get('lr', 0.1 * a.base_lr),
-           'val_fp32': a.val_fp32,
+           'val_fp32': a.val_fp32, 'eval_only': a.eval_only, 'extra': a.extra,
            'data': 'synthetic polyp frames (datasets/synthetic.py), MyConfig augmentation on the GPU (DeviceAugLoader)',
            'process_wall_s': round(time.time() - t0, 1),
            **summarise(os.path.join(save, 'val_history.json'), a.target)}
