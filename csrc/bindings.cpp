@@ -1398,6 +1398,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv_set_gemm", [](bool on) { conv_gemm_set(on ? 1 : 0); });
   m.def("conv_gemm_force_cfg", [](int64_t c) { conv_gemm_force_cfg((int)c); });
   m.def("conv_gemm_num_cfgs", []() { return conv_gemm_num_cfgs(); });
+  m.def("conv_gemm_stamp_buffer", [](c10::optional<at::Tensor> buf) {
+    if (!buf.has_value()) return conv_gemm_stamp_buffer(nullptr, 0);
+    TORCH_CHECK(buf->is_cuda() && buf->is_contiguous() && buf->scalar_type() == at::kLong && buf->dim() == 2 &&
+                    buf->size(1) == 4, "conv_gemm_stamp_buffer: a contiguous int64 [blocks][4] device tensor");
+    return conv_gemm_stamp_buffer(buf->data_ptr(), buf->size(0));
+  });
   m.def("conv_set_wgrad_gemm", [](int64_t mode) { conv_wgrad_gemm_set((int)mode); });
   m.def("conv_wgrad_gemm_force_cfg", [](int64_t c) { conv_wgrad_gemm_force_cfg((int)c); });
   m.def("conv_wgrad_gemm_num_cfgs", []() { return conv_wgrad_gemm_num_cfgs(); });

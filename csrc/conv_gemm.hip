@@ -15,7 +15,13 @@
 //   * the LDS image is XOR-swizzled on the source side (16-B slot ^= (row >> 1) & 7): the 16 rows of a
 //     ds_read_b128 lane group then sit on 16 distinct bank slots -> conflict-free fragment reads.
 // Pipeline: 2 LDS stages; the DMA of stage k+1 is issued before the MFMAs of stage k, one
-// vmcnt(0) + barrier per stage.
+// vmcnt(0) + barrier per stage.  Nothing between a stage's DMA instructions may read vector memory: until
+// round 7 the per-lane choice of the input group pointer compiled to a vector load + vmcnt(0) between the A and
+// the B instructions of every stage (see stage()).  Every tile is its own block: a persistent block walking
+// several tiles as one K-stage stream, the next tile's first stages in flight during the epilogue, was built
+// in round 7, computed the same bits and lost at every level 3-6 layer -- the prefetch hides only the first
+// stage's latency, not the per-tile set-up or the epilogue (profiles/r07/persistent_gemm/README.md; the
+// -DGK_STAMP clock readings it was judged by stay in the kernel).
 // Epilogue: bias / accumulate / bf16 round, 8-B NHWC stores into the row's output group, and the
 // per-channel BatchNorm partials (sum, sum^2 of the stored values -- or, for the data-gradient of a
 // BN output, the BN-backward partials) reduced across lanes and waves in LDS, one row per pixel tile.
@@ -67,6 +73,17 @@ DEVI void glds16(const void* src, uint32_t lds) {
 
 typedef __attribute__((address_space(3))) uint8_t lds_u8_t;
 
+#ifdef GK_STAMP   // (profiling build only: csrc/build.py MSP_BUILD_DEFINES; never the product build)
+// the 100-MHz constant clock, fenced so that it is read where it stands
+DEVI unsigned long long gk_clock() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+#endif
+
 
 struct KPos { int t, gi, cl; };
 
@@ -96,6 +113,10 @@ struct GemmGeom {
   int ps, py, px, OWp;
   long OHWp, OW, OHWf;
   long apitch;   // packed weight row pitch (= Kp; a phase launch walks K = its own taps, rows keep the full pitch)
+#ifdef GK_STAMP
+  unsigned long long* stamp;   // [stamp_cap][4] clock readings per block: entry, first MFMA, last MFMA, exit
+  long stamp_cap;
+#endif
 };
 
 // BK = k per stage (64 or 32): one staged row (co or pixel) is BK bf16 = ROWB bytes, one DMA instruction
@@ -144,6 +165,10 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_gemm_kernel(ConvArgs a
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t sbase = (uint32_t)(uintptr_t)(lds_u8_t*)smem;   // LDS byte address of the stages
+#ifdef GK_STAMP
+  const unsigned long long ts0 = gk_clock();
+  unsigned long long ts1 = ts0;
+#endif
 
   // XCD-aware bijective remap: the co tiles of one pixel tile (which share its B operand) and
   // neighbouring pixel tiles (which share input rows through the tap halo) run on one XCD's L2
@@ -227,6 +252,9 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_gemm_kernel(ConvArgs a
     for (int u = 1; u < kMaxGroups; ++u) xb = q == u ? a.x[u] : xb;
     return xb;
   };
+  // the input pointers of group g0 and of the group after it (walk state: see stage())
+  const uint16_t* xg0 = gptr(g0);
+  const uint16_t* xg1 = gptr(g0 + 1 == Gi ? 0 : g0 + 1);
 
   const int Cip_ = Gi * Cgi;
   auto stage = [&](int kt, uint32_t sb) {
@@ -250,7 +278,18 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_gemm_kernel(ConvArgs a
 #pragma unroll
     for (int j = 0; j < C::A_INS; ++j) glds16(a_src[j] + ka, sb + (RPI * (j * C::NW + wave)) * kRowB);
     const int t = nx ? t1 : t0;
+    // The two group pointers are walk state, pinned in SGPRs before the per-lane choice.  Left to itself the
+    // compiler folds "nx ? gptr(g1) : gptr(g0)" into ONE per-lane indexed vector load from the
+    // kernel-argument segment, waits for it with vmcnt(0) and so drains every DMA in flight between the A
+    // and the B instructions of EVERY stage -- the memory read between two LDS-DMAs that TapGrid warns
+    // about.  (Pinned but looked up per stage, two scalar loads and their wait still sat between the A and
+    // the B instructions: 2.4 % slower over the level 3-6 layers.  profiles/r07/persistent_gemm/README.md)
+#ifdef GK_OLD_XSEL   // (profiling build only: the per-lane select as it was, for a before / after on one tree)
     const uint16_t* base = (nx ? gptr(g1) : gptr(g0)) + (nx ? toff1 + (8 * ls - rem0) : toff0 + (cl0 + 8 * ls));
+#else
+    asm volatile("" : "+s"(xg0), "+s"(xg1));
+    const uint16_t* base = (nx ? xg1 : xg0) + (nx ? toff1 + (8 * ls - rem0) : toff0 + (cl0 + 8 * ls));
+#endif
     const bool tin = t < 32;
 #pragma unroll
     for (int j = 0; j < C::B_INS; ++j) {
@@ -260,7 +299,11 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_gemm_kernel(ConvArgs a
     }
     // advance the walk by BK (at most one boundary: Cgi >= 64)
     cl0 += BK;
-    if (cl0 >= Cgi) { cl0 -= Cgi; g0 = g1; t0 = t1; tr0 = tr1; tc0 = tc1; toff0 = toff1; }
+    if (cl0 >= Cgi) {
+      cl0 -= Cgi; g0 = g1; t0 = t1; tr0 = tr1; tc0 = tc1; toff0 = toff1;
+      xg0 = xg1;   // (the look-up of the next group's pointer lands behind this stage's DMAs)
+      xg1 = gptr(g0 + 1 == Gi ? 0 : g0 + 1);
+    }
   };
 
   // ---- fragment reads: lane (r = lane & 31, h = lane >> 5) takes 8 k at logical slot 2s + h of row r
@@ -301,6 +344,9 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_gemm_kernel(ConvArgs a
     __builtin_amdgcn_sched_barrier(0);
     if (kt + NS - 1 < nk) stage(kt + NS - 1, sbase + ((kt + NS - 1) % NS) * C::STAGE);
     const uint8_t* cur = smem + (kt % NS) * C::STAGE;
+#ifdef GK_STAMP
+    if (kt == 0) ts1 = gk_clock();
+#endif
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       uint4 af[FM], bfr[FN];
@@ -321,6 +367,9 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_gemm_kernel(ConvArgs a
     }
   }
   __syncthreads();   // every wave is done with the stages before the epilogue reuses them
+#ifdef GK_STAMP
+  const unsigned long long ts2 = gk_clock();
+#endif
 
   // ---- epilogue.  32x32 D layout: lane holds column (pixel) lr, rows 8q + 4h + r in register 4q + r.
   float* s_st = reinterpret_cast<float*>(smem);   // [WN][2][TCO] per-pixel-wave-column channel partials
@@ -436,6 +485,13 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_gemm_kernel(ConvArgs a
       a.stat_part[(srow * 2 + 1) * rows + co] = q;
     }
   }
+#ifdef GK_STAMP   // one lane's four readings, to a buffer nothing else in the kernel touches
+  const unsigned long long ts3 = gk_clock();
+  if (tid == 0 && gg.stamp != nullptr && wgid < gg.stamp_cap) {
+    unsigned long long* sp = gg.stamp + 4 * (long)wgid;
+    sp[0] = ts0; sp[1] = ts1; sp[2] = ts2; sp[3] = ts3;
+  }
+#endif
 }
 
 // ---- configurations ------------------------------------------------------------------------------
@@ -524,6 +580,11 @@ struct GemmPhase {
   int akw = 0, ar0 = 0, ars = 1, ac0 = 0, acs = 1;   // akw 0: identity remap
 };
 
+#ifdef GK_STAMP
+unsigned long long* g_stamp = nullptr;   // conv_gemm_stamp_buffer
+long g_stamp_cap = 0;
+#endif
+
 template <int WM, int WN, int FM, int FN, int NS, int BK, bool BNE, int OCC = 2>
 void launch_gemm(const ConvArgs& a, const GemmPhase& ph, hipStream_t s) {
   using C = GemmCfg<WM, WN, FM, FN, NS, BK>;
@@ -537,6 +598,9 @@ void launch_gemm(const ConvArgs& a, const GemmPhase& ph, hipStream_t s) {
   gg.OHWp = gg.OHW; gg.OW = ph.OWf; gg.OHWf = (long)ph.OHf * ph.OWf;
   gg.apitch = ph.apitch > 0 ? ph.apitch : g.Kp;
   const long blocks = (long)cdiv(gg.M, C::TPX) * gg.n_co;
+#ifdef GK_STAMP
+  gg.stamp = g_stamp; gg.stamp_cap = g_stamp_cap;
+#endif
   static bool attr = false;
   if (!attr) {   // > 64 KB dynamic LDS: opted into once per instantiation, before any graph capture
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<WM, WN, FM, FN, NS, BK, BNE, OCC>),
@@ -604,6 +668,18 @@ static int gemm_tile_for(const ConvGeom& g) {
 void conv_gemm_set(int on) { gemm_env(); g_gemm_mode = on ? 1 : 0; }
 void conv_gemm_force_cfg(int cfg) { gemm_env(); g_gemm_cfg = (cfg >= 0 && cfg < kNumCfgs) ? cfg : -1; }
 int conv_gemm_num_cfgs() { return kNumCfgs; }
+// GK_STAMP builds: the buffer the kernel's clock readings go to ([cap][4] 64-bit words, one row per block;
+// nullptr: none).  Returns whether this build stamps at all.
+int conv_gemm_stamp_buffer(void* buf, long cap) {
+#ifdef GK_STAMP
+  g_stamp = static_cast<unsigned long long*>(buf);
+  g_stamp_cap = buf != nullptr ? cap : 0;
+  return 1;
+#else
+  (void)buf; (void)cap;
+  return 0;
+#endif
+}
 
 long conv_gemm_stat_blocks(const ConvGeom& g) { return cdiv((long)g.N * g.OH * g.OW, kGemmTPX); }
 

@@ -106,6 +106,9 @@ int conv_gemm_phase(const ConvArgs& a, const int* tA, int KW, int s_, int py, in
 void conv_gemm_set(int on);
 void conv_gemm_force_cfg(int cfg);   // tests / A-B: one tile configuration for every launch (-1: planner)
 int conv_gemm_num_cfgs();
+// GK_STAMP profiling builds: [cap][4] 64-bit clock readings per block (entry, first MFMA, last MFMA, exit);
+// returns 0 in a build without stamps
+int conv_gemm_stamp_buffer(void* buf, long cap);
 // dw: fp32 [Go*Cgo][T*Cip] (overwritten)
 int conv_plan_selfcheck(int verbose);   // host-only launch-planner invariants (sanitizer harness)
 int conv_wgrad_replicas(const ConvGeom& g, bool trans, bool bwd = false, bool pro = false);   // bwd: see conv_wgrad

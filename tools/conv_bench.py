@@ -53,6 +53,25 @@ def timeit(fn, iters):
     return s.elapsed_time(e) / iters
 
 
+def stamp_summary(C, buf, fn):
+    """One stamped call (GK_STAMP build): per block the clock readings entry / first MFMA / last MFMA / exit
+    (100-MHz ticks).  Returns the median fill, main-loop and drain time in us, the fill + drain share of the
+    block lifetime and the number of blocks stamped."""
+    buf.zero_()
+    C.conv_gemm_stamp_buffer(buf)
+    fn()
+    torch.cuda.synchronize()
+    C.conv_gemm_stamp_buffer(None)
+    t = buf[buf[:, 3] > 0].double() * 0.01
+    if t.shape[0] == 0:
+        return None
+    fill, loop, drain = t[:, 1] - t[:, 0], t[:, 2] - t[:, 1], t[:, 3] - t[:, 2]
+    life = (t[:, 3] - t[:, 0]).sum().item()
+    return {'fill_us': round(fill.median().item(), 2), 'loop_us': round(loop.median().item(), 2),
+            'drain_us': round(drain.median().item(), 2), 'blocks': int(t.shape[0]),
+            'fill_drain_share': round((fill.sum().item() + drain.sum().item()) / max(life, 1e-9), 4)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=16)
@@ -63,6 +82,9 @@ def main():
     ap.add_argument('--split', type=int, default=1, help='halo split-bank tile image: 0 never, 1 occupancy-preserving '
                     '(default), 2 wherever it fits (csrc/conv.hip halo_phys)')
     ap.add_argument('--gemm-cfg', type=int, default=-1, help='force one LDS-DMA GEMM tile configuration (A/B)')
+    ap.add_argument('--gemm-stamps', action='store_true',
+                    help='in-kernel clock stamps per block (needs a -DGK_STAMP side build loaded through MSP_C_SO): '
+                    'median fill / main loop / drain per layer, forward and data-gradient')
     ap.add_argument('--only', default='', help='substring filter on layer names')
     ap.add_argument('--levels', default='', help='comma list of levels to run (e.g. 3,4,5,6)')
     ap.add_argument('--prologue', action='store_true',
@@ -74,6 +96,11 @@ def main():
     C.conv_set_halo(bool(a.halo))
     C.conv_set_halo_split(a.split)
     C.conv_gemm_force_cfg(a.gemm_cfg)
+    sbuf = None
+    if a.gemm_stamps:
+        if not C.conv_gemm_stamp_buffer(None):
+            sys.exit('--gemm-stamps: this extension was built without -DGK_STAMP')
+        sbuf = torch.zeros(1 << 18, 4, device=dev, dtype=torch.int64)
     res = []
     tot = {'fwd': 0.0, 'dgrad': 0.0, 'wgrad': 0.0}
     for name, lvl, ci, co, k, s, p, d, groups in layers():
@@ -118,6 +145,16 @@ def main():
             xm = torch.randn(n, ci, hw, hw, device=dev, dtype=torch.bfloat16).contiguous(memory_format=torch.channels_last)
             wm = torch.randn(co * groups, ci, *k, device=dev, dtype=torch.bfloat16).contiguous(memory_format=torch.channels_last)
             row['miopen_fwd_ms'] = round(timeit(lambda: F.conv2d(xm, wm, None, s, p, d), a.iters), 4)
+        if sbuf is not None:
+            row['stamps_fwd'] = stamp_summary(
+                C, sbuf, lambda: C.conv_fwd([x], wp, ys, None, part, dims, dy, dx, False, xc, xr))
+            row['stamps_dgrad'] = stamp_summary(
+                C, sbuf, lambda: C.conv_fwd(gys, wd, dxs, None, None, dims_d, bdy, bdx, s > 1))
+            for k in ('stamps_fwd', 'stamps_dgrad'):
+                if row[k]:
+                    print(f"    {k[7:]:5s} fill {row[k]['fill_us']:6.2f} us  loop {row[k]['loop_us']:7.2f}  drain "
+                          f"{row[k]['drain_us']:6.2f}  fill+drain share {100 * row[k]['fill_drain_share']:5.1f} %  "
+                          f"({row[k]['blocks']} blocks)", flush=True)
         row['halo_fwd'] = bool(C.conv_uses_halo(dims, dy, dx, False))
         row['halo_dgrad'] = bool(C.conv_uses_halo(dims_d, bdy, bdx, s > 1))
         res.append(row)
