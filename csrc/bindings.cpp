@@ -560,10 +560,14 @@ void colorize_t(const at::Tensor& logits, const at::Tensor& lut, const at::Tenso
 }
 
 // ---- GPU augmentation (augment.hip)
-void aug_batch_t(const at::Tensor& images, const at::Tensor& masks, const at::Tensor& meta, const at::Tensor& ip,
-                 const at::Tensor& fp, const at::Tensor& work, const at::Tensor& mean, const at::Tensor& out,
-                 const at::Tensor& mask_out, std::vector<int64_t> stages, std::vector<int64_t> contrast_stages,
-                 std::vector<double> norm_mean, std::vector<double> norm_std) {
+// `ops`: union of the kAug* flags that occur in the batch (0: the plain pipeline, no extra tables); xi / xf /
+// work2 are only read when the matching bit is set
+static void aug_batch_run(const at::Tensor& images, const at::Tensor& masks, const at::Tensor& meta,
+                          const at::Tensor& ip, const at::Tensor& fp, const at::Tensor& work, const at::Tensor& mean,
+                          const at::Tensor& out, const at::Tensor& mask_out, const std::vector<int64_t>& stages,
+                          const std::vector<int64_t>& contrast_stages, const std::vector<double>& norm_mean,
+                          const std::vector<double>& norm_std, int ops, const at::Tensor* xi, const at::Tensor* xf,
+                          const at::Tensor* work2) {
   TORCH_CHECK(images.is_cuda() && images.scalar_type() == at::kByte && images.is_contiguous());
   TORCH_CHECK(masks.is_cuda() && masks.scalar_type() == at::kByte && masks.is_contiguous());
   CHECK_I64(meta); CHECK_I64(mask_out); CHECK_F32(fp); CHECK_F32(work); CHECK_F32(mean); CHECK_F32(out);
@@ -577,8 +581,22 @@ void aug_batch_t(const at::Tensor& images, const at::Tensor& masks, const at::Te
   TORCH_CHECK(work.numel() == (int64_t)B * H * W * 3 && mask_out.numel() == (int64_t)B * H * W);
   TORCH_CHECK(meta.dim() == 2 && meta.size(1) == 4 && norm_mean.size() == 3 && norm_std.size() == 3);
   auto s = cur_stream();
-  aug_geometry(images.data_ptr<uint8_t>(), masks.data_ptr<uint8_t>(), meta.data_ptr<int64_t>(), ip.data_ptr<int>(),
-               f32(work), mask_out.data_ptr<int64_t>(), B, H, W, s);
+  if (ops) {
+    TORCH_CHECK(xi && xi->is_cuda() && xi->scalar_type() == at::kInt && xi->is_contiguous() &&
+                xi->numel() == (int64_t)B * kAugXI, "aug: xi int32 [B, kAugXI]");
+    TORCH_CHECK(xf && xf->numel() == (int64_t)B * kAugXF, "aug: xf fp32 [B, kAugXF]");
+    CHECK_F32((*xf));
+    if (ops & kAugBlur) {
+      TORCH_CHECK(work2 && work2->numel() >= work.numel(), "aug: blur needs a second work buffer");
+      CHECK_F32((*work2));
+    }
+  }
+  if (ops & kAugWarp)
+    aug_warp(images.data_ptr<uint8_t>(), masks.data_ptr<uint8_t>(), meta.data_ptr<int64_t>(), ip.data_ptr<int>(),
+             xi->data_ptr<int>(), f32(*xf), f32(work), mask_out.data_ptr<int64_t>(), B, H, W, s);
+  else
+    aug_geometry(images.data_ptr<uint8_t>(), masks.data_ptr<uint8_t>(), meta.data_ptr<int64_t>(), ip.data_ptr<int>(),
+                 f32(work), mask_out.data_ptr<int64_t>(), B, H, W, s);
   for (size_t k = 0; k < stages.size(); ++k) {
     const int st = (int)stages[k];
     TORCH_CHECK(st >= 0 && st < 4);
@@ -588,7 +606,76 @@ void aug_batch_t(const at::Tensor& images, const at::Tensor& masks, const at::Te
   }
   const float m3[3] = {(float)norm_mean[0], (float)norm_mean[1], (float)norm_mean[2]};
   const float s3[3] = {(float)norm_std[0], (float)norm_std[1], (float)norm_std[2]};
-  aug_finalize(f32(work), ip.data_ptr<int>(), f32(out), B, H * W, m3, s3, s);
+  // gamma -> blur -> noise; without a blur in the batch gamma and noise share one launch
+  const float* cur = f32(work);
+  if (ops & kAugBlur) {
+    if (ops & kAugGamma) aug_pointwise(f32(work), xi->data_ptr<int>(), f32(*xf), B, H * W, kAugGamma, s);
+    aug_blur(f32(work), f32(*work2), xi->data_ptr<int>(), f32(*xf), B, H, W, s);
+    if (ops & kAugNoise) aug_pointwise(f32(*work2), xi->data_ptr<int>(), f32(*xf), B, H * W, kAugNoise, s);
+    cur = f32(*work2);
+  } else if (ops & (kAugGamma | kAugNoise)) {
+    aug_pointwise(f32(work), xi->data_ptr<int>(), f32(*xf), B, H * W, ops & (kAugGamma | kAugNoise), s);
+  }
+  aug_finalize(cur, ip.data_ptr<int>(), f32(out), B, H * W, m3, s3, s);
+}
+
+void aug_batch_t(const at::Tensor& images, const at::Tensor& masks, const at::Tensor& meta, const at::Tensor& ip,
+                 const at::Tensor& fp, const at::Tensor& work, const at::Tensor& mean, const at::Tensor& out,
+                 const at::Tensor& mask_out, std::vector<int64_t> stages, std::vector<int64_t> contrast_stages,
+                 std::vector<double> norm_mean, std::vector<double> norm_std) {
+  aug_batch_run(images, masks, meta, ip, fp, work, mean, out, mask_out, stages, contrast_stages, norm_mean, norm_std,
+                0, nullptr, nullptr, nullptr);
+}
+
+// aug_batch for a batch in which some sample warps or takes gamma / blur / noise (`ops` != 0)
+void aug_batch_ex_t(const at::Tensor& images, const at::Tensor& masks, const at::Tensor& meta, const at::Tensor& ip,
+                    const at::Tensor& fp, const at::Tensor& xi, const at::Tensor& xf, const at::Tensor& work,
+                    const c10::optional<at::Tensor>& work2, const at::Tensor& mean, const at::Tensor& out,
+                    const at::Tensor& mask_out, std::vector<int64_t> stages, std::vector<int64_t> contrast_stages,
+                    std::vector<double> norm_mean, std::vector<double> norm_std, int64_t ops) {
+  TORCH_CHECK(ops > 0 && ops < 2 * kAugConstant, "aug_batch_ex: ops is a non-empty union of the kAug* flags");
+  aug_batch_run(images, masks, meta, ip, fp, work, mean, out, mask_out, stages, contrast_stages, norm_mean, norm_std,
+                (int)ops, &xi, &xf, work2.has_value() ? &work2.value() : nullptr);
+}
+
+// single launches of the gather / warp / pointwise / blur kernels (tools/augment_bench.py times them)
+void aug_gather_t(const at::Tensor& images, const at::Tensor& masks, const at::Tensor& meta, const at::Tensor& ip,
+                  const c10::optional<at::Tensor>& xi, const c10::optional<at::Tensor>& xf, const at::Tensor& work,
+                  const at::Tensor& mask_out, int64_t H, int64_t W) {
+  TORCH_CHECK(images.is_cuda() && images.scalar_type() == at::kByte && images.is_contiguous());
+  TORCH_CHECK(masks.is_cuda() && masks.scalar_type() == at::kByte && masks.is_contiguous());
+  CHECK_I64(meta); CHECK_I64(mask_out); CHECK_F32(work);
+  TORCH_CHECK(ip.is_cuda() && ip.scalar_type() == at::kInt && ip.is_contiguous() && ip.numel() % kAugIParams == 0);
+  const int B = ip.numel() / kAugIParams;
+  TORCH_CHECK(work.numel() == (int64_t)B * H * W * 3 && mask_out.numel() == (int64_t)B * H * W);
+  if (xi.has_value()) {
+    TORCH_CHECK(xf.has_value() && xi->is_cuda() && xi->scalar_type() == at::kInt && xi->is_contiguous() &&
+                xi->numel() == (int64_t)B * kAugXI && xf->numel() == (int64_t)B * kAugXF);
+    CHECK_F32((*xf));
+    aug_warp(images.data_ptr<uint8_t>(), masks.data_ptr<uint8_t>(), meta.data_ptr<int64_t>(), ip.data_ptr<int>(),
+             xi->data_ptr<int>(), f32(*xf), f32(work), mask_out.data_ptr<int64_t>(), B, H, W, cur_stream());
+  } else {
+    aug_geometry(images.data_ptr<uint8_t>(), masks.data_ptr<uint8_t>(), meta.data_ptr<int64_t>(), ip.data_ptr<int>(),
+                 f32(work), mask_out.data_ptr<int64_t>(), B, H, W, cur_stream());
+  }
+}
+
+void aug_pointwise_t(const at::Tensor& work, const at::Tensor& xi, const at::Tensor& xf, int64_t HW, int64_t ops) {
+  CHECK_F32(work); CHECK_F32(xf);
+  TORCH_CHECK(xi.is_cuda() && xi.scalar_type() == at::kInt && xi.is_contiguous() && xi.numel() % kAugXI == 0);
+  const int B = xi.numel() / kAugXI;
+  TORCH_CHECK(xf.numel() == (int64_t)B * kAugXF && work.numel() == (int64_t)B * HW * 3);
+  aug_pointwise(f32(work), xi.data_ptr<int>(), f32(xf), B, HW, (int)ops, cur_stream());
+}
+
+void aug_blur_t(const at::Tensor& in, const at::Tensor& out, const at::Tensor& xi, const at::Tensor& xf, int64_t H,
+                int64_t W) {
+  CHECK_F32(in); CHECK_F32(out); CHECK_F32(xf);
+  TORCH_CHECK(xi.is_cuda() && xi.scalar_type() == at::kInt && xi.is_contiguous() && xi.numel() % kAugXI == 0);
+  const int B = xi.numel() / kAugXI;
+  TORCH_CHECK(xf.numel() == (int64_t)B * kAugXF && in.numel() == (int64_t)B * H * W * 3 &&
+              out.numel() == in.numel() && in.data_ptr() != out.data_ptr());
+  aug_blur(f32(in), f32(out), xi.data_ptr<int>(), f32(xf), B, H, W, cur_stream());
 }
 
 void scale_f32_t(const at::Tensor& x, const c10::optional<at::Tensor>& scalar, double mult) {
@@ -1470,6 +1557,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("bilinear_resize", &bilinear_resize_t);
   m.def("colorize", &colorize_t);
   m.def("aug_iparams", []() { return kAugIParams; });
+  m.def("aug_batch_ex", &aug_batch_ex_t);
+  m.def("aug_gather", &aug_gather_t);
+  m.def("aug_pointwise", &aug_pointwise_t);
+  m.def("aug_blur", &aug_blur_t);
+  m.def("aug_xparams", []() { return std::make_pair(kAugXI, kAugXF); });
+  m.def("aug_flags", []() {
+    return std::vector<int>{kAugWarp, kAugElastic, kAugGamma, kAugBlur, kAugNoise, kAugConstant};
+  });
   m.def("maxpool_fwd", &maxpool_fwd_t);
   m.def("maxpool_bwd", &maxpool_bwd_t);
   m.def("up2_cat", &up2_cat_t);

@@ -220,6 +220,15 @@ void aug_color(float* work, const int* ip, const float* fp, const float* mean, i
                hipStream_t s);
 void aug_finalize(const float* work, const int* ip, float* out, int B, int HW, const float* mean3, const float* std3,
                   hipStream_t s);
+// rotation / shift / elastic warp, gamma, blur, noise: per-sample tables xi (int32) and xf (fp32), see augment.hip
+constexpr int kAugXI = 8;
+constexpr int kAugXF = 264;
+enum : int { kAugWarp = 1, kAugElastic = 2, kAugGamma = 4, kAugBlur = 8, kAugNoise = 16, kAugConstant = 32 };
+void aug_warp(const uint8_t* images, const uint8_t* masks, const int64_t* meta, const int* ip, const int* xi,
+              const float* xf, float* work, int64_t* mask_out, int B, int CH, int CW, hipStream_t s);
+// gamma and / or noise in place, for the samples whose flags have a bit of `ops` (kAugGamma | kAugNoise)
+void aug_pointwise(float* work, const int* xi, const float* xf, int B, int HW, int ops, hipStream_t s);
+void aug_blur(const float* in, float* out, const int* xi, const float* xf, int B, int CH, int CW, hipStream_t s);
 
 // loss.hip  (logits NCHW fp32 [N, C, HW]; targets int64 [N, HW])
 long ce_blocks(long P);

@@ -125,6 +125,22 @@ class BaseConfig:
         self.saturation = 0.0
         self.h_flip = 0.0
         self.v_flip = 0.0
+        # rotation / shift / elastic warp and gamma / blur / noise (utils/transforms.SegAugment, csrc/augment.hip;
+        # absent from the reference).  Every group is off at its default and then draws no random number.
+        self.aug_rotate = 0.0          # rotation limit in degrees: theta ~ U[-r, r]
+        self.aug_shift = 0.0           # translation limit as a fraction of the crop
+        self.aug_affine_p = 0.5        # probability of the rotate / shift group
+        self.aug_elastic_sigma = 0.0   # std (pixels) of the B-spline control-point displacements; 0 = off
+        self.aug_elastic_cells = 4     # B-spline cells per axis over the crop, 1..8
+        self.aug_elastic_p = 0.5
+        self.aug_border = 'reflect'    # 'reflect' (reflect-101) | 'constant' (zeros) outside the scaled image,
+                                       # for warped samples
+        self.aug_gamma = None          # None | [lo, hi]: gamma ~ U[lo, hi], v <- 255 (v / 255)^gamma
+        self.aug_gamma_p = 0.5
+        self.aug_blur_sigma = None     # None | [lo, hi] pixels, hi <= 2.5: Gaussian blur
+        self.aug_blur_p = 0.5
+        self.aug_noise_std = None      # None | [lo, hi] in 0..255 levels: additive Gaussian noise
+        self.aug_noise_p = 0.5
 
         # DDP
         self.synBN = True
@@ -220,7 +236,46 @@ class BaseConfig:
             self.num_class = 2 if self.num_class == -1 else self.num_class
             self.num_channel = 3 if self.num_channel is None else self.num_channel
         self._auto_derived = auto
+        self.check_augment()           # after crop_h / crop_w are derived: the blur radius is checked against them
         return self
+
+    def check_augment(self):
+        """Validate the rotation / shift / elastic / gamma / blur / noise fields; ranges become ``(lo, hi)``."""
+        for name in ('aug_affine_p', 'aug_elastic_p', 'aug_gamma_p', 'aug_blur_p', 'aug_noise_p'):
+            if not 0.0 <= float(getattr(self, name)) <= 1.0:
+                raise ValueError(f'{name} must be in [0, 1], got {getattr(self, name)!r}')
+        if not 0.0 <= float(self.aug_rotate) <= 180.0:
+            raise ValueError(f'aug_rotate must be in [0, 180] degrees, got {self.aug_rotate!r}')
+        if not 0.0 <= float(self.aug_shift) <= 1.0:
+            raise ValueError(f'aug_shift must be in [0, 1] (a fraction of the crop), got {self.aug_shift!r}')
+        if not 0.0 <= float(self.aug_elastic_sigma) <= 64.0:
+            raise ValueError(f'aug_elastic_sigma must be in [0, 64] pixels, got {self.aug_elastic_sigma!r}')
+        if int(self.aug_elastic_cells) != self.aug_elastic_cells or not 1 <= self.aug_elastic_cells <= 8:
+            raise ValueError(f'aug_elastic_cells must be an integer in 1..8, got {self.aug_elastic_cells!r}')
+        if self.aug_border not in ('reflect', 'constant'):
+            raise ValueError(f"aug_border must be 'reflect' or 'constant', got {self.aug_border!r}")
+
+        def pair(name, lo_min, hi_max, lo_open=False):
+            v = getattr(self, name)
+            if v is None:
+                return None
+            v = list(v) if isinstance(v, (tuple, list)) else [v, v]
+            if (len(v) != 2 or not all(isinstance(x, (int, float)) for x in v) or v[0] > v[1] or v[0] < lo_min
+                    or (lo_open and v[0] <= lo_min) or v[1] > hi_max):
+                raise ValueError(f"{name} must be [lo, hi] with {lo_min} {'<' if lo_open else '<='} lo <= hi <= "
+                                 f'{hi_max}, got {getattr(self, name)!r}')
+            setattr(self, name, (float(v[0]), float(v[1])))
+            return getattr(self, name)
+
+        pair('aug_gamma', 0.0, 10.0, lo_open=True)
+        pair('aug_noise_std', 0.0, 255.0)
+        blur = pair('aug_blur_sigma', 0.0, 2.5, lo_open=True)
+        if blur is not None and self.crop_h is not None and self.crop_w is not None:
+            import math
+            radius = min(int(math.ceil(3.0 * blur[1])), 8)
+            if 2 * radius >= min(self.crop_h, self.crop_w):
+                raise ValueError(f'aug_blur_sigma {blur!r}: twice the blur radius ({radius}) must be below the crop '
+                                 f'({self.crop_h} x {self.crop_w})')
 
     INFERENCE_FIELDS = ('infer_window', 'infer_overlap', 'infer_blend', 'infer_sigma_scale', 'infer_batch',
                         'tta_flips', 'tta_average')

@@ -113,6 +113,19 @@ def get_parser():
     _flag(p, 'saturation', type=float)
     _flag(p, 'h_flip', type=float)
     _flag(p, 'v_flip', type=float)
+    _flag(p, 'aug_rotate', type=float)
+    _flag(p, 'aug_shift', type=float)
+    _flag(p, 'aug_affine_p', type=float)
+    _flag(p, 'aug_elastic_sigma', type=float)
+    _flag(p, 'aug_elastic_cells', type=int)
+    _flag(p, 'aug_elastic_p', type=float)
+    _flag(p, 'aug_border', type=str, choices=['reflect', 'constant'])
+    _flag(p, 'aug_gamma', type=float, nargs=2)
+    _flag(p, 'aug_gamma_p', type=float)
+    _flag(p, 'aug_blur_sigma', type=float, nargs=2)
+    _flag(p, 'aug_blur_p', type=float)
+    _flag(p, 'aug_noise_std', type=float, nargs=2)
+    _flag(p, 'aug_noise_p', type=float)
     # DDP
     _flag(p, 'synBN', action='store_false')
     _flag(p, 'destroy_ddp_process', action='store_false')

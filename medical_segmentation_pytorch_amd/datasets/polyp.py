@@ -13,6 +13,10 @@ from torch.utils.data import Dataset
 
 from ..utils.transforms import SegAugment, normalize_to_tensor
 
+MEDICAL_AUG_FIELDS = ('aug_rotate', 'aug_shift', 'aug_affine_p', 'aug_elastic_sigma', 'aug_elastic_cells',
+                      'aug_elastic_p', 'aug_border', 'aug_gamma', 'aug_gamma_p', 'aug_blur_sigma', 'aug_blur_p',
+                      'aug_noise_std', 'aug_noise_p')
+
 
 class PolypDataset(Dataset):
     def __init__(self, config, mode='train'):
@@ -38,9 +42,12 @@ class PolypDataset(Dataset):
         self.mode = mode
         self.binary_float = config.num_class == 1
         if mode == 'train':
+            # the rotation / elastic / gamma / blur / noise fields are optional: a config without them (an older
+            # one, a bare namespace) gets SegAugment's defaults, i.e. every such option off
+            medical = {k: getattr(config, k) for k in MEDICAL_AUG_FIELDS if hasattr(config, k)}
             self.transform = SegAugment(config.crop_h, config.crop_w, config.randscale, config.brightness,
                                         config.contrast, config.saturation, h_flip=config.h_flip,
-                                        v_flip=config.v_flip)
+                                        v_flip=config.v_flip, **medical)
         else:
             self.transform = None
 
