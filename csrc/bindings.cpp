@@ -925,6 +925,81 @@ void surface_finalize_t(const at::Tensor& stats, const at::Tensor& sums, const a
                 onesided.data_ptr<int64_t>(), pi, (int)N, (int)K, (int)H, (int)W, cur_stream());
 }
 
+// ---- signed distance map + boundary loss (surface.hip sdf_*, loss.hip boundary_*)
+static SdfClasses sdf_classes(const std::vector<int64_t>& classes, int64_t C) {
+  TORCH_CHECK(C >= 2 && C <= kSdfMaxClasses, "boundary loss: num_class must be in [2, ", kSdfMaxClasses, "], got ", C);
+  TORCH_CHECK(!classes.empty() && (int64_t)classes.size() <= C, "classes must list 1 .. num_class distinct classes");
+  SdfClasses cls;
+  for (int c = 0; c < kSdfMaxClasses; ++c) { cls.c[c] = 0; cls.plane[c] = -1; }
+  for (size_t k = 0; k < classes.size(); ++k) {
+    const int64_t c = classes[k];
+    TORCH_CHECK(c >= 0 && c < C, "class ", c, " outside [0, ", C, ")");
+    TORCH_CHECK(cls.plane[c] < 0, "class ", c, " listed twice");
+    cls.c[k] = (uint8_t)c;
+    cls.plane[c] = (int8_t)k;
+  }
+  return cls;
+}
+
+void sdf_sq_t(const at::Tensor& target, const at::Tensor& s, const std::vector<int64_t>& classes, int64_t C,
+              int64_t ignore_index) {
+  CHECK_I64(target); CHECK_I32(s);
+  TORCH_CHECK(target.dim() == 3, "target must be [N, H, W]");
+  const int64_t N = target.size(0), H = target.size(1), W = target.size(2), K = (int64_t)classes.size();
+  const SdfClasses cls = sdf_classes(classes, C);
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= kSdfMaxDim && W <= kSdfMaxDim, "signed distance: H and W must be in [1, ",
+              kSdfMaxDim, "], got ", H, " x ", W);
+  TORCH_CHECK(N >= 1 && N * K * H <= 2147483647LL, "signed distance: too many rows in one call");
+  TORCH_CHECK(s.numel() == N * K * H * W, "s must be [N, K, H, W]");
+  sdf_sq(target.data_ptr<int64_t>(), s.data_ptr<int32_t>(), cls, (int)K, (int)N, (int)C, (int)H, (int)W,
+         (int)ignore_index, cur_stream());
+}
+
+void sdf_phi_t(const at::Tensor& s, const at::Tensor& phi) {
+  CHECK_I32(s); CHECK_F32(phi);
+  TORCH_CHECK(phi.numel() == s.numel(), "phi must be shaped like s");
+  if (s.numel() > 0) sdf_phi(s.data_ptr<int32_t>(), f32(phi), s.numel(), cur_stream());
+}
+
+int64_t boundary_blocks_t(int64_t P) { return boundary_blocks(P); }
+
+// shared checks of the two boundary-loss passes; returns {N, C, HW}
+static std::tuple<int, int, long> boundary_check(const at::Tensor& logits, const at::Tensor& target,
+                                                 const at::Tensor& s, int64_t K) {
+  CHECK_F32(logits); CHECK_I64(target); CHECK_I32(s);
+  TORCH_CHECK(logits.dim() == 4, "logits must be NCHW");
+  const int64_t N = logits.size(0), C = logits.size(1), HW = logits.size(2) * logits.size(3);
+  TORCH_CHECK(N >= 1 && HW >= 1 && target.numel() == N * HW, "target must be [N, H, W]");
+  TORCH_CHECK(s.numel() == N * K * HW, "s must be [N, K, H, W]");
+  return {(int)N, (int)C, (long)HW};
+}
+
+void boundary_fwd_t(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& s,
+                    const std::vector<int64_t>& classes, const at::Tensor& part, const at::Tensor& loss,
+                    const at::Tensor& norm, int64_t ignore_index) {
+  const int64_t K = (int64_t)classes.size();
+  const auto [N, C, HW] = boundary_check(logits, target, s, K);
+  const SdfClasses cls = sdf_classes(classes, C);
+  CHECK_F32(part); CHECK_F32(loss); CHECK_F32(norm);
+  TORCH_CHECK(part.numel() == 2 * (int64_t)boundary_blocks((long)N * HW), "part must be [boundary_blocks(N H W), 2]");
+  TORCH_CHECK(loss.numel() == 1 && norm.numel() == 1, "loss and norm must be [1]");
+  boundary_fwd(f32(logits), target.data_ptr<int64_t>(), s.data_ptr<int32_t>(), cls, (int)K, f32(part), f32(loss),
+               f32(norm), N, C, HW, (int)ignore_index, cur_stream());
+}
+
+void boundary_grad_t(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& s,
+                     const std::vector<int64_t>& classes, const at::Tensor& norm, const at::Tensor& gup,
+                     const at::Tensor& grad, int64_t ignore_index) {
+  const int64_t K = (int64_t)classes.size();
+  const auto [N, C, HW] = boundary_check(logits, target, s, K);
+  const SdfClasses cls = sdf_classes(classes, C);
+  CHECK_F32(norm); CHECK_F32(gup); CHECK_F32(grad);
+  TORCH_CHECK(norm.numel() == 1 && gup.numel() == 1 && grad.numel() == logits.numel(),
+              "norm [1], gup [1], grad like logits");
+  boundary_grad(f32(logits), target.data_ptr<int64_t>(), s.data_ptr<int32_t>(), cls, (int)K, f32(norm), f32(gup),
+                f32(grad), N, C, HW, (int)ignore_index, cur_stream());
+}
+
 // ---- connected components (components.hip)
 static void cc_planes_check(const at::Tensor& lab, const at::Tensor& root, const at::Tensor& area,
                             const at::Tensor& aux) {
@@ -1601,6 +1676,12 @@ PYBIND11_MODULE(_C, m) {
         py::arg("onesided"), py::arg("per_image"), py::arg("N"), py::arg("K"), py::arg("H"), py::arg("W"));
   m.attr("EDT_MAX_DIM") = kEdtMaxDim;
   m.attr("EDT_NONE") = kEdtNone;
+  m.def("sdf_sq", &sdf_sq_t);
+  m.def("sdf_phi", &sdf_phi_t);
+  m.attr("SDF_MAX_DIM") = kSdfMaxDim;
+  m.def("boundary_blocks", &boundary_blocks_t);
+  m.def("boundary_fwd", &boundary_fwd_t);
+  m.def("boundary_grad", &boundary_grad_t);
   m.def("cc_label", &cc_label_t, py::arg("lab"), py::arg("root"), py::arg("area"), py::arg("aux"), py::arg("err"),
         py::arg("half") = 0, py::arg("connectivity") = 8, py::arg("mode") = 0);
   m.def("cc_rank", &cc_rank_t);

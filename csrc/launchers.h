@@ -262,6 +262,22 @@ void region_finalize(const float* part, float* coef, float* loss, int N, int C, 
 void region_grad(const float* logits, const int64_t* target, const float* weight, const float* coef,
                  const float* gup, float* grad, int N, int C, long HW, int ignore_index, int pix, float gamma,
                  float pw, float rw, float a, float b, int c0, hipStream_t s);
+// boundary (signed-distance) term on the softmax: sum over valid pixels and the K listed classes of p_c * phi_c,
+// divided by K * max(V, 1) (V = valid pixels of the batch); phi from the signed squared distance s [N][K][HW] of
+// sdf_sq (surface.hip).  A kernel argument by value carries the class list both ways.
+constexpr int kSdfMaxClasses = 64;   // == region_max_classes()
+struct SdfClasses {
+  uint8_t c[kSdfMaxClasses];         // class of plane k (k < K)
+  int8_t plane[kSdfMaxClasses];      // plane of class c, -1 if the class is not listed
+};
+// part [boundary_blocks(N * HW)][2] = {sum p * phi, valid pixels} per block; finalize (one block, fixed order, fp64):
+// loss [1] and norm [1] = 1 / (K * max(V, 1)).  grad = gup * norm * p_k (phi~_k - sum_c p_c phi~_c), 0 where invalid.
+int boundary_blocks(long P);
+void boundary_fwd(const float* logits, const int64_t* target, const int32_t* sdf, const SdfClasses& cls, int K,
+                  float* part, float* loss, float* norm, int N, int C, long HW, int ignore_index, hipStream_t s);
+void boundary_grad(const float* logits, const int64_t* target, const int32_t* sdf, const SdfClasses& cls, int K,
+                   const float* norm, const float* gup, float* grad, int N, int C, long HW, int ignore_index,
+                   hipStream_t s);
 
 // optim.hip  (flat fp32 buffers; hyper = device fp32 array, see optim.hip for the layout)
 void adam_step(float* p, const float* g, float* m, float* v, const float* hyper, long n, int adamw,
@@ -301,6 +317,14 @@ void surf_reduce(int32_t* d2, int64_t* stats, double* sums, long B, long HW, int
 // per_image (nullable) [N][K][3].
 void surf_finalize(const int64_t* stats, const double* sums, double* sum, int64_t* count, int64_t* onesided,
                    double* per_image, int N, int K, int H, int W, hipStream_t s);
+// Signed squared distance of int64 labels target [N][H][W] (H, W <= kSdfMaxDim) to s [N][K][H][W], plane k for
+// class cls.c[k]: +d^2 to the nearest pixel of the class at the other valid pixels, -d^2 to the nearest other valid
+// pixel inside the class, 0 at invalid pixels and in a plane where either set is empty.  s is also the scratch.
+constexpr int kSdfMaxDim = 2048;   // d^2 <= 2 * 2048^2 = 2^23: exact in fp32
+void sdf_sq(const int64_t* target, int32_t* s, const SdfClasses& cls, int K, int N, int C, int H, int W,
+            int ignore_index, hipStream_t st);
+// phi = sqrt(s) for s > 0, 1 - sqrt(-s) for s < 0, 0 for s == 0 (correctly rounded fp32 root)
+void sdf_phi(const int32_t* s, float* phi, long n, hipStream_t st);
 
 // components.hip: connected-component labelling of uint8 label planes [B][H][W] (H, W <= kEdtMaxDim), mask clean-up
 // and lesion-wise counters.  A pixel equal to kCcSkip belongs to nothing; any other pixel is connected to a 4- or

@@ -10,6 +10,8 @@
 //   region_*      : softmax heads (num_class >= 2): CE | focal pixel term + per-sample, per-class soft
 //                   Dice | Tversky on the softmax; statistics pass, one-block finalize (coefficients and
 //                   loss stay on the device), gradient pass.
+//   boundary_*    : softmax heads: the softmax integrated against the signed distance map of the labels
+//                   (surface.hip sdf_sq); forward partials, one-block finalize, gradient pass.
 // Partials are per block ([nblk][2] = {weighted loss sum, weight sum}); the host sums them.
 #include "common.h"
 #include "launchers.h"
@@ -679,6 +681,176 @@ __global__ __launch_bounds__(kBlock) void region_grad_generic_kernel(
 bool region_vec_ok(const void* x, const void* t, const void* g, long HW) {
   return HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)t | (uintptr_t)g) & 15) == 0;
 }
+
+// ---- boundary (signed-distance) term: L = sum_{valid x, k < K} p_{c_k}(x) phi_k(x) / (K max(V, 1)), phi from the
+// signed squared distance s [N][K][HW] (surface.hip sdf_sq): sqrt(s), 1 - sqrt(-s), 0.  The integer is exact in
+// fp32 and the root correctly rounded, so phi is the same number wherever it is evaluated.  (sqrtf, not
+// __fsqrt_rn: the HIP headers map the latter to the native, approximate root.)
+//   boundary_fwd_*    : softmax in registers (C = 2, 3, 4) or re-read (generic), part[b] = {sum p phi, #valid}
+//   boundary_finalize : one block adds the partials in a fixed order (fp64) -> loss and norm = 1 / (K max(V, 1))
+//   boundary_grad_*   : dx_k = gup norm p_k (phi~_k - sum_c p_c phi~_c), phi~ = 0 for unlisted classes; 0 if invalid
+DEVI float sdf_phi_of(int v) { return v > 0 ? sqrtf((float)v) : (v < 0 ? 1.f - sqrtf((float)-v) : 0.f); }
+
+DEVI void boundary_block_out(float acc, float cnt, float* part) {
+  __shared__ float red[2][kBlock / 64];
+  acc = wave_sum(acc);
+  cnt = wave_sum(cnt);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = acc; red[1][threadIdx.x >> 6] = cnt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float a = 0.f, b = 0.f;
+    for (int w = 0; w < kBlock / 64; ++w) { a += red[0][w]; b += red[1][w]; }
+    part[2 * blockIdx.x] = a;
+    part[2 * blockIdx.x + 1] = b;
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(kBlock) void boundary_fwd_kernel(const float* __restrict__ logits,
+                                                              const int64_t* __restrict__ target,
+                                                              const int* __restrict__ sdf, SdfClasses cls, int K,
+                                                              float* __restrict__ part, long P, long HW,
+                                                              int ignore_index) {
+  float acc = 0.f, cnt = 0.f;
+  for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < P; i += (long)gridDim.x * kBlock) {
+    if (!region_valid(target[i], C, ignore_index)) continue;
+    const long n = i / HW, p = i - n * HW;
+    const float* xs = logits + n * C * HW + p;
+    const int* sp = sdf + n * K * HW + p;
+    float x[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) x[c] = xs[c * HW];
+    float m = x[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
+    float se = 0.f, dot = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float e = __expf(x[c] - m);
+      se += e;
+      const int k = cls.plane[c];
+      if (k >= 0) dot += e * sdf_phi_of(sp[k * HW]);
+    }
+    acc += dot / se;
+    cnt += 1.f;
+  }
+  boundary_block_out(acc, cnt, part);
+}
+
+__global__ __launch_bounds__(kBlock) void boundary_fwd_generic_kernel(const float* __restrict__ logits,
+                                                                      const int64_t* __restrict__ target,
+                                                                      const int* __restrict__ sdf, SdfClasses cls,
+                                                                      int K, float* __restrict__ part, long P, int C,
+                                                                      long HW, int ignore_index) {
+  float acc = 0.f, cnt = 0.f;
+  for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < P; i += (long)gridDim.x * kBlock) {
+    if (!region_valid(target[i], C, ignore_index)) continue;
+    const long n = i / HW, p = i - n * HW;
+    const float* xs = logits + n * C * HW + p;
+    const int* sp = sdf + n * K * HW + p;
+    float m = -INFINITY;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, xs[c * HW]);
+    float se = 0.f, dot = 0.f;
+    for (int c = 0; c < C; ++c) se += __expf(xs[c * HW] - m);
+    for (int k = 0; k < K; ++k) dot += __expf(xs[cls.c[k] * HW] - m) * sdf_phi_of(sp[k * HW]);
+    acc += dot / se;
+    cnt += 1.f;
+  }
+  boundary_block_out(acc, cnt, part);
+}
+
+__global__ __launch_bounds__(kFinBlock) void boundary_finalize_kernel(const float* __restrict__ part, int nblk, int K,
+                                                                       float* __restrict__ loss,
+                                                                       float* __restrict__ norm) {
+  __shared__ double red[2][kFinBlock];
+  double s = 0.0, v = 0.0;
+  for (int b = threadIdx.x; b < nblk; b += kFinBlock) { s += part[2 * b]; v += part[2 * b + 1]; }
+  red[0][threadIdx.x] = s;
+  red[1][threadIdx.x] = v;
+  __syncthreads();
+  for (int h = kFinBlock / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + h];
+      red[1][threadIdx.x] += red[1][threadIdx.x + h];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double V = red[1][0] > 1.0 ? red[1][0] : 1.0;
+    const double k = 1.0 / ((double)K * V);
+    loss[0] = (float)(red[0][0] * k);
+    norm[0] = (float)k;
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(kBlock) void boundary_grad_kernel(const float* __restrict__ logits,
+                                                               const int64_t* __restrict__ target,
+                                                               const int* __restrict__ sdf, SdfClasses cls, int K,
+                                                               const float* __restrict__ norm,
+                                                               const float* __restrict__ gup, float* __restrict__ grad,
+                                                               long P, long HW, int ignore_index) {
+  const float g0 = gup[0] * norm[0];
+  for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < P; i += (long)gridDim.x * kBlock) {
+    const long n = i / HW, p = i - n * HW;
+    float* gs = grad + n * C * HW + p;
+    if (!region_valid(target[i], C, ignore_index)) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) gs[c * HW] = 0.f;
+      continue;
+    }
+    const float* xs = logits + n * C * HW + p;
+    const int* sp = sdf + n * K * HW + p;
+    float x[C], e[C], ph[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) x[c] = xs[c * HW];
+    float m = x[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
+    float se = 0.f, dot = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      e[c] = __expf(x[c] - m);
+      se += e[c];
+      const int k = cls.plane[c];
+      ph[c] = k >= 0 ? sdf_phi_of(sp[k * HW]) : 0.f;
+      dot += e[c] * ph[c];
+    }
+    const float inv = 1.f / se;
+    dot *= inv;
+#pragma unroll
+    for (int c = 0; c < C; ++c) gs[c * HW] = g0 * (e[c] * inv) * (ph[c] - dot);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void boundary_grad_generic_kernel(
+    const float* __restrict__ logits, const int64_t* __restrict__ target, const int* __restrict__ sdf, SdfClasses cls,
+    int K, const float* __restrict__ norm, const float* __restrict__ gup, float* __restrict__ grad, long P, int C,
+    long HW, int ignore_index) {
+  const float g0 = gup[0] * norm[0];
+  for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < P; i += (long)gridDim.x * kBlock) {
+    const long n = i / HW, p = i - n * HW;
+    float* gs = grad + n * C * HW + p;
+    if (!region_valid(target[i], C, ignore_index)) {
+      for (int c = 0; c < C; ++c) gs[c * HW] = 0.f;
+      continue;
+    }
+    const float* xs = logits + n * C * HW + p;
+    const int* sp = sdf + n * K * HW + p;
+    float m = -INFINITY;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, xs[c * HW]);
+    float se = 0.f, dot = 0.f;
+    for (int c = 0; c < C; ++c) se += __expf(xs[c * HW] - m);
+    for (int k = 0; k < K; ++k) dot += __expf(xs[cls.c[k] * HW] - m) * sdf_phi_of(sp[k * HW]);
+    const float inv = 1.f / se;
+    dot *= inv;
+    for (int c = 0; c < C; ++c) {
+      const int k = cls.plane[c];
+      const float ph = k >= 0 ? sdf_phi_of(sp[k * HW]) : 0.f;
+      gs[c * HW] = g0 * (__expf(xs[c * HW] - m) * inv) * (ph - dot);
+    }
+  }
+}
 }  // namespace
 
 long ce_blocks(long P) {
@@ -741,6 +913,43 @@ void ohem_backward(float* grad, const float* pix_loss, const unsigned* state, co
                    hipStream_t s) {
   hipLaunchKernelGGL(ohem_bwd_kernel, dim3(ce_blocks((long)N * HW)), dim3(kBlock), 0, s, grad, pix_loss, state, gup,
                      N, C, HW);
+}
+
+int boundary_blocks(long P) { return (int)ce_blocks(P); }
+
+void boundary_fwd(const float* logits, const int64_t* target, const int32_t* sdf, const SdfClasses& cls, int K,
+                  float* part, float* loss, float* norm, int N, int C, long HW, int ignore_index, hipStream_t s) {
+  const long P = (long)N * HW;
+  const int nblk = boundary_blocks(P);
+  const dim3 grid(nblk), block(kBlock);
+#define BOUNDARY_FWD(CC)                                                                                          \
+  hipLaunchKernelGGL((boundary_fwd_kernel<CC>), grid, block, 0, s, logits, target, sdf, cls, K, part, P, HW,      \
+                     ignore_index)
+  if (C == 2) BOUNDARY_FWD(2);
+  else if (C == 3) BOUNDARY_FWD(3);
+  else if (C == 4) BOUNDARY_FWD(4);
+  else
+    hipLaunchKernelGGL(boundary_fwd_generic_kernel, grid, block, 0, s, logits, target, sdf, cls, K, part, P, C, HW,
+                       ignore_index);
+#undef BOUNDARY_FWD
+  hipLaunchKernelGGL(boundary_finalize_kernel, dim3(1), dim3(kFinBlock), 0, s, part, nblk, K, loss, norm);
+}
+
+void boundary_grad(const float* logits, const int64_t* target, const int32_t* sdf, const SdfClasses& cls, int K,
+                   const float* norm, const float* gup, float* grad, int N, int C, long HW, int ignore_index,
+                   hipStream_t s) {
+  const long P = (long)N * HW;
+  const dim3 grid(boundary_blocks(P)), block(kBlock);
+#define BOUNDARY_GRAD(CC)                                                                                         \
+  hipLaunchKernelGGL((boundary_grad_kernel<CC>), grid, block, 0, s, logits, target, sdf, cls, K, norm, gup, grad, \
+                     P, HW, ignore_index)
+  if (C == 2) BOUNDARY_GRAD(2);
+  else if (C == 3) BOUNDARY_GRAD(3);
+  else if (C == 4) BOUNDARY_GRAD(4);
+  else
+    hipLaunchKernelGGL(boundary_grad_generic_kernel, grid, block, 0, s, logits, target, sdf, cls, K, norm, gup, grad,
+                       P, C, HW, ignore_index);
+#undef BOUNDARY_GRAD
 }
 
 int region_max_classes() { return kMaxC; }

@@ -86,6 +86,10 @@ class BaseConfig:
         self.tversky_alpha = 0.3       # false-positive weight
         self.tversky_beta = 0.7        # false-negative weight
         self.focal_gamma = 2.0         # 0 (plain ce) or >= 1
+        # boundary (signed-distance) term of the '*boundary' loss types (core.loss.BoundaryLoss)
+        self.loss_boundary_weight = 0.01      # >= 0
+        self.boundary_ramp_epochs = 0         # weight * min(1, (epoch + 1) / R) for R > 0
+        self.boundary_include_background = False   # True: class 0 gets a distance map as well
 
         # Scheduler
         self.lr_policy = 'cos_warmup'
@@ -213,6 +217,12 @@ class BaseConfig:
             raise ValueError(f'cc_connectivity must be 4 or 8, got {self.cc_connectivity!r}')
         if int(self.post_min_area) != self.post_min_area or self.post_min_area < 0:
             raise ValueError(f'post_min_area must be an integer >= 0, got {self.post_min_area!r}')
+        if isinstance(self.loss_boundary_weight, bool) or not isinstance(self.loss_boundary_weight, (int, float)) \
+                or not self.loss_boundary_weight >= 0:
+            raise ValueError(f'loss_boundary_weight must be a number >= 0, got {self.loss_boundary_weight!r}')
+        if isinstance(self.boundary_ramp_epochs, bool) or not isinstance(self.boundary_ramp_epochs, (int, float)) \
+                or int(self.boundary_ramp_epochs) != self.boundary_ramp_epochs or self.boundary_ramp_epochs < 0:
+            raise ValueError(f'boundary_ramp_epochs must be an integer >= 0, got {self.boundary_ramp_epochs!r}')
         self.check_inference()
         auto = getattr(self, '_auto_derived', set())
 

@@ -69,7 +69,13 @@ def get_parser():
     _flag(p, 'post_keep_largest', action='store_true')
     # Loss
     _flag(p, 'loss_type', type=str, choices=['ce', 'ohem', 'bce', 'dice', 'bce_dice', 'tversky', 'focal', 'ce_dice',
-                                             'ce_tversky', 'focal_dice', 'focal_tversky'])
+                                             'ce_tversky', 'focal_dice', 'focal_tversky', 'boundary', 'ce_boundary',
+                                             'focal_boundary', 'dice_boundary', 'tversky_boundary',
+                                             'ce_dice_boundary', 'ce_tversky_boundary', 'focal_dice_boundary',
+                                             'focal_tversky_boundary'])
+    _flag(p, 'loss_boundary_weight', type=float)
+    _flag(p, 'boundary_ramp_epochs', type=int)
+    _flag(p, 'boundary_include_background', action='store_true')
     _flag(p, 'loss_pixel_weight', type=float)
     _flag(p, 'loss_region_weight', type=float)
     _flag(p, 'dice_smooth', type=float)

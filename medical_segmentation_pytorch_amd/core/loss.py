@@ -4,7 +4,9 @@ On a ROCm device with the HIP extension the CE / OHEM / KD-KL losses run the fus
 kernels of ``csrc/loss.hip`` (loss + gradient in one pass); elsewhere plain PyTorch with identical
 semantics.  Added (north star): ``'bce_dice'`` for ``num_class == 1``, and for
 softmax heads (``num_class >= 2``) the overlap / focal family of :class:`RegionLoss`: ``dice``,
-``tversky``, ``focal``, ``ce_dice``, ``ce_tversky``, ``focal_dice``, ``focal_tversky``.
+``tversky``, ``focal``, ``ce_dice``, ``ce_tversky``, ``focal_dice``, ``focal_tversky``.  Each of those, and the
+empty base, can carry the boundary (signed-distance) term of :class:`BoundaryLoss`: ``boundary``,
+``ce_boundary``, ``ce_dice_boundary`` and so on.
 """
 from __future__ import annotations
 
@@ -140,8 +142,84 @@ class RegionLoss(nn.Module):
         return loss
 
 
+def boundary_weight_at(epoch, weight, ramp_epochs):
+    """Weight of the boundary term in 0-based ``epoch``: ``weight * min(1, (epoch + 1) / ramp_epochs)`` for
+    ``ramp_epochs > 0`` (the "increase" schedule of the paper), ``weight`` for 0.  A function of the epoch alone,
+    so a resumed run needs nothing from the checkpoint."""
+    if ramp_epochs <= 0:
+        return float(weight)
+    return float(weight) * min(1.0, (int(epoch) + 1) / float(ramp_epochs))
+
+
+class BoundaryLoss(nn.Module):
+    """``base(logits, labels) + w * L_B`` for softmax heads: ``base`` an optional :class:`RegionLoss`, ``L_B`` the
+    boundary loss of Kervadec et al. (MIDL 2019),
+
+        ``L_B = sum_{n, c in S, valid x} p_c(x) * phi_nc(x) / (|S| * max(V, 1))``
+
+    with ``p = softmax(logits)``, ``phi`` the signed distance map of ``ops.surface.signed_distance`` (negative
+    inside class ``c``, positive outside, 0 at invalid pixels and for a class absent from or filling the image),
+    ``S`` the foreground classes (all classes with ``include_background``) and ``V`` the number of valid pixels of
+    the batch (the :class:`RegionLoss` rule).  No valid pixel: ``L_B`` is 0 with zero gradient.  A mean over the
+    rank's own pixels: nothing is exchanged under DDP.
+
+    ``w`` lives in the one-element buffer ``bw`` on the device, so a captured graph reads the current value:
+    :meth:`set_epoch` fills it with ``weight * min(1, (epoch + 1) / ramp_epochs)`` (``weight`` when
+    ``ramp_epochs == 0``) and no re-capture is needed.  On a ROCm device with the HIP extension ``L_B`` is
+    ``ops.losses.boundary_loss``; elsewhere the plain-torch form below, in the input's floating dtype."""
+
+    def __init__(self, base=None, weight=0.01, ramp_epochs=0, ignore_index=255, include_background=False,
+                 device=None):
+        super().__init__()
+        if base is not None and not isinstance(base, RegionLoss):
+            raise ValueError(f'BoundaryLoss: base must be a RegionLoss or None, got {type(base).__name__}')
+        if not float(weight) >= 0:
+            raise ValueError(f'loss_boundary_weight must be >= 0, got {weight!r}')
+        if int(ramp_epochs) != ramp_epochs or ramp_epochs < 0:
+            raise ValueError(f'boundary_ramp_epochs must be an integer >= 0, got {ramp_epochs!r}')
+        self.base, self.weight, self.ramp_epochs = base, float(weight), int(ramp_epochs)
+        self.ignore_index, self.include_background = ignore_index, bool(include_background)
+        self.register_buffer('bw', torch.full((1,), boundary_weight_at(0, weight, ramp_epochs), dtype=torch.float32,
+                                              device=device), persistent=False)
+
+    def set_epoch(self, epoch):
+        self.bw.fill_(boundary_weight_at(epoch, self.weight, self.ramp_epochs))
+
+    def classes(self, num_class):
+        return list(range(0 if self.include_background else 1, num_class))
+
+    def boundary_term(self, logits, labels):
+        cls = self.classes(logits.shape[1])
+        if _fused_ok(logits):
+            from ..ops.losses import boundary_loss
+            return boundary_loss(logits.float(), labels, self.ignore_index, cls)
+        from ..ops.surface import signed_distance
+        x = logits if logits.dtype in (torch.float32, torch.float64) else logits.float()
+        C = x.shape[1]
+        valid = (labels != self.ignore_index) & (labels >= 0) & (labels < C)
+        phi = signed_distance(labels, C, self.ignore_index, cls).to(x.dtype)     # 0 at invalid pixels
+        V = valid.sum().clamp_min(1).to(x.dtype)
+        return (F.softmax(x, 1)[:, cls] * phi).sum() / (len(cls) * V)
+
+    def forward(self, logits, labels):
+        lb = self.boundary_term(logits, labels)
+        loss = self.bw.to(lb.dtype).reshape(()) * lb
+        return loss if self.base is None else self.base(logits, labels) + loss
+
+
 _PIXEL_TERMS, _REGION_TERMS = ('ce', 'focal'), ('dice', 'tversky')
 REGION_LOSS_TYPES = ('dice', 'tversky', 'focal', 'ce_dice', 'ce_tversky', 'focal_dice', 'focal_tversky')
+BOUNDARY_LOSS_TYPES = ('boundary', 'ce_boundary', 'focal_boundary', 'dice_boundary', 'tversky_boundary',
+                       'ce_dice_boundary', 'ce_tversky_boundary', 'focal_dice_boundary', 'focal_tversky_boundary')
+
+
+def _region_loss_of(terms, config, weights):
+    pixel = next((k for k in terms if k in _PIXEL_TERMS), None)
+    region = next((k for k in terms if k in _REGION_TERMS), None)
+    return RegionLoss(pixel, region, ignore_index=config.ignore_index, weight=weights,
+                      pixel_weight=config.loss_pixel_weight, region_weight=config.loss_region_weight,
+                      smooth=config.dice_smooth, alpha=config.tversky_alpha, beta=config.tversky_beta,
+                      gamma=config.focal_gamma, ignore_background=config.dice_ignore_background)
 
 
 def get_loss_fn(config, device):
@@ -164,13 +242,16 @@ def get_loss_fn(config, device):
         if not multi:
             raise ValueError(f"loss_type '{lt}' needs a softmax head, but num_class = {config.num_class}; "
                              f"use 'bce', 'dice' or 'bce_dice'")
-        terms = lt.split('_')
-        pixel = next((k for k in terms if k in _PIXEL_TERMS), None)
-        region = next((k for k in terms if k in _REGION_TERMS), None)
-        return RegionLoss(pixel, region, ignore_index=config.ignore_index, weight=weights,
-                          pixel_weight=config.loss_pixel_weight, region_weight=config.loss_region_weight,
-                          smooth=config.dice_smooth, alpha=config.tversky_alpha, beta=config.tversky_beta,
-                          gamma=config.focal_gamma, ignore_background=config.dice_ignore_background)
+        return _region_loss_of(lt.split('_'), config, weights)
+    if lt in BOUNDARY_LOSS_TYPES:
+        if not multi:
+            raise ValueError(f"loss_type '{lt}' needs a softmax head (the boundary term integrates the softmax "
+                             f"against per-class distance maps), but num_class = {config.num_class}")
+        terms = lt.split('_')[:-1]
+        base = _region_loss_of(terms, config, weights) if terms else None
+        return BoundaryLoss(base, weight=config.loss_boundary_weight, ramp_epochs=config.boundary_ramp_epochs,
+                            ignore_index=config.ignore_index, include_background=config.boundary_include_background,
+                            device=device)
     raise NotImplementedError(f'Unsupport loss type: {lt}')
 
 

@@ -189,6 +189,8 @@ class SegTrainer(BaseTrainer):
         self.config_ref = config
         self.model.train()
         sampler_set_epoch(config, self.train_loader, self.cur_epoch)
+        if hasattr(self.loss_fn, 'set_epoch'):
+            self.loss_fn.set_epoch(self.cur_epoch)     # epoch-scheduled loss weights (BoundaryLoss)
         pbar = _tqdm(self.train_loader, self.main_rank and config.progress_bar)
         wd = getattr(self, 'watchdog', None)
         for cur_itrs, (images, masks) in enumerate(pbar):

@@ -18,6 +18,9 @@
   statistics pass plus a one-block finalize (coefficient table and loss scalar stay on the device);
   backward is one gradient pass that recomputes the softmax.  No atomics, no host read: bitwise
   repeatable and graph-capturable like the others.
+* :func:`boundary_loss`: the softmax integrated against the signed distance map of the labels (the
+  plain-torch form is ``core.loss.BoundaryLoss``); the map comes from ``csrc/surface.hip`` inside the
+  same call and is kept as int32 squared distances for the gradient pass.
 """
 from __future__ import annotations
 
@@ -200,6 +203,53 @@ class _Region(torch.autograd.Function):
         grad = torch.empty_like(x)
         require().region_grad(x, t, weight, coef, g.detach().float().reshape(1).contiguous(), grad, *ctx.args)
         return (grad,) + (None,) * 11
+
+
+class _Boundary(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, classes):
+        C = require()
+        x = logits.contiguous().float()
+        t = target.contiguous().long()
+        n, c, h, w = x.shape
+        dev = x.device
+        s = torch.empty(n, len(classes), h, w, dtype=torch.int32, device=dev)
+        C.sdf_sq(t, s, classes, c, ignore_index)
+        part = torch.empty(C.boundary_blocks(n * h * w), 2, dtype=torch.float32, device=dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)        # loss, 1 / (K max(V, 1))
+        C.boundary_fwd(x, t, s, classes, part, out[:1], out[1:], ignore_index)
+        ctx.save_for_backward(x, t, s, out)
+        ctx.args = (ignore_index, classes)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t, s, out = ctx.saved_tensors
+        ignore_index, classes = ctx.args
+        grad = torch.empty_like(x)
+        require().boundary_grad(x, t, s, classes, out[1:], g.detach().float().reshape(1).contiguous(), grad,
+                                ignore_index)
+        return grad, None, None, None
+
+
+def boundary_loss(logits, target, ignore_index=255, classes=None):
+    """Boundary loss (Kervadec et al., MIDL 2019) on fp32 NCHW logits and int64 ``[N, H, W]`` labels:
+    ``sum_{n, c in classes, valid x} softmax(logits)_c(x) * phi_nc(x) / (len(classes) * max(V, 1))`` with ``phi``
+    the signed distance map of ``ops.surface.signed_distance`` (negative inside class ``c``; 0 for a class that is
+    absent from or fills the image) and ``V`` the valid pixels of the batch.  ``classes`` defaults to
+    ``1 .. C-1``.  The distance map is computed on the device from the labels of this call (column + row pass),
+    then one pass for the loss and one for the gradient; no atomics, no host read: bitwise repeatable and
+    graph-capturable.  A mean over the rank's own valid pixels, like ``cross_entropy``: nothing is exchanged
+    under DDP.  H, W <= 2048, C <= 64."""
+    from .surface import _check_sdf_hw, _sdf_classes
+    if logits.dim() != 4 or target.shape != logits.shape[:1] + logits.shape[2:]:
+        raise ValueError(f'boundary_loss: logits [N, C, H, W] and target [N, H, W], got {tuple(logits.shape)} and '
+                         f'{tuple(target.shape)}')
+    if logits.shape[1] > 64:
+        raise RuntimeError(f'boundary loss: num_class must be in [2, 64], got {logits.shape[1]}')
+    cls = _sdf_classes(logits.shape[1], classes)
+    _check_sdf_hw(logits.shape[2], logits.shape[3])
+    return _Boundary.apply(logits, target, int(ignore_index), cls)
 
 
 def region_loss(logits, target, weight=None, ignore_index=255, pixel='ce', region='dice', pixel_weight=1.0,

@@ -216,6 +216,118 @@ def edt_sq(mask):
     return out.view(mask.shape)
 
 
+SDF_MAX_DIM = 2048          # signed_distance: d^2 <= 2 * 2048^2 = 2^23, exact in fp32
+SDF_MAX_CLASSES = 64
+
+
+def _sdf_classes(num_classes, classes):
+    if not 2 <= num_classes <= SDF_MAX_CLASSES:
+        raise ValueError(f'signed distance: num_classes must be in [2, {SDF_MAX_CLASSES}], got {num_classes}')
+    cls = list(range(1, num_classes)) if classes is None else [int(c) for c in classes]
+    if not cls or len(set(cls)) != len(cls) or min(cls) < 0 or max(cls) >= num_classes:
+        raise ValueError(f'signed distance: classes must be distinct values in [0, {num_classes}), got {classes!r}')
+    return cls
+
+
+def _check_sdf_hw(h, w):
+    if h < 1 or w < 1 or h > SDF_MAX_DIM or w > SDF_MAX_DIM:
+        raise ValueError(f'signed distance: H and W must be in [1, {SDF_MAX_DIM}], got {h} x {w}')
+
+
+_SDF_COL_NONE = 1 << 15     # vertical "no such pixel in this column"; its square 2^30 exceeds every real d^2
+
+
+def _col_dist(m):
+    """bool [B, H, W] -> int32 vertical distance to the nearest set pixel of the column (_SDF_COL_NONE: none)."""
+    h = m.shape[1]
+    y = torch.arange(h, device=m.device, dtype=torch.int32).view(1, h, 1)
+    far = torch.full_like(y, -2 * _SDF_COL_NONE).expand_as(m)     # |y -+ far| > _SDF_COL_NONE for every row
+    above = torch.where(m, y.expand_as(m), far).cummax(1).values                      # last set row <= y
+    below = -torch.where(m, -y.expand_as(m), far).flip(1).cummax(1).values.flip(1)    # first set row >= y
+    return torch.minimum(y - above, below - y).clamp_max(_SDF_COL_NONE)
+
+
+def _row_min(g2, chunk=1 << 24):
+    """int32 [B, H, W] squared vertical field -> min over x' of (x - x')^2 + g2[.., x'] (broadcast, rows in chunks)."""
+    b, h, w = g2.shape
+    x = torch.arange(w, device=g2.device, dtype=torch.int32)
+    dx2 = (x.view(w, 1) - x.view(1, w)) ** 2
+    flat = g2.reshape(b * h, w)
+    out = torch.empty_like(flat)
+    step = max(1, chunk // (w * w))
+    for i in range(0, flat.shape[0], step):
+        out[i:i + step] = (flat[i:i + step, None, :] + dx2).min(-1).values
+    return out.view(b, h, w)
+
+
+def _signed_distance_sq_torch(labels, num_classes, ignore_index, cls):
+    t = labels.long()
+    n, h, w = t.shape
+    valid = (t >= 0) & (t < num_classes)
+    if ignore_index is not None:
+        valid &= t != ignore_index
+    sel = torch.tensor(cls, device=t.device).view(1, -1, 1, 1)
+    pos = (valid.unsqueeze(1) & (t.unsqueeze(1) == sel)).reshape(-1, h, w)
+    neg = (valid.unsqueeze(1) & (t.unsqueeze(1) != sel)).reshape(-1, h, w)
+    live = (pos.flatten(1).any(1) & neg.flatten(1).any(1)).view(-1, 1, 1)
+    to_pos = _row_min(_col_dist(pos) ** 2)
+    to_neg = _row_min(_col_dist(neg) ** 2)
+    zero = torch.zeros_like(to_pos)
+    s = torch.where(neg, to_pos, zero) - torch.where(pos, to_neg, zero)
+    return torch.where(live, s, zero).view(n, len(cls), h, w)
+
+
+def _sqrt_rn_f32(v):
+    """Correctly rounded fp32 square root of integers ``0 <= v < 2^24``.  ``torch.sqrt`` on fp32 is not correctly
+    rounded on every CPU (its vector kernels allow slightly more than half an ulp), so the candidate from the fp64
+    root is checked against its two rounding boundaries: those are 25-bit numbers, so their squares are exact in
+    fp64, and one step to the neighbour settles a candidate that lies on the wrong side."""
+    v64 = v.double()
+    r = v64.sqrt().float()
+    up = torch.nextafter(r, torch.full_like(r, float('inf')))
+    dn = torch.nextafter(r, torch.full_like(r, float('-inf')))
+    hi, lo = (r.double() + up.double()) * 0.5, (r.double() + dn.double()) * 0.5
+    return torch.where(v64 > hi * hi, up, torch.where((v64 < lo * lo) & (r > 0), dn, r))
+
+
+def _phi_torch(s):
+    f = _sqrt_rn_f32(s.abs())
+    return torch.where(s > 0, f, torch.where(s < 0, 1.0 - f, torch.zeros_like(f)))
+
+
+def signed_distance(labels, num_classes, ignore_index=None, classes=None, squared=False):
+    """Signed distance map of integer labels ``[N, H, W]`` per class of ``classes`` (default ``1 .. C-1``):
+    ``[N, len(classes), H, W]``.
+
+    A pixel is valid iff ``label != ignore_index and 0 <= label < num_classes``.  Per image and class ``c``,
+    ``pos`` = valid pixels labelled ``c`` and ``neg`` = the other valid pixels.  ``squared=True`` gives the exact
+    int32 ``s``: ``+d^2`` to the nearest ``pos`` pixel at a ``neg`` pixel (>= 1), ``-d^2`` to the nearest ``neg``
+    pixel at a ``pos`` pixel (<= -1), 0 at an invalid pixel (distances are measured across those), and 0
+    everywhere in a plane whose ``pos`` or ``neg`` set is empty.  Otherwise the fp32 signed distance
+    ``phi = sqrt(s)`` (s > 0), ``1 - sqrt(-s)`` (s < 0), ``0``, i.e. ``edt(neg) * neg - (edt(pos) - 1) * pos`` with
+    scipy's ``distance_transform_edt`` (the root is the correctly rounded fp32 one; ``|s| <= 2^23`` is exact).
+    H, W <= ``SDF_MAX_DIM``.  On the GPU with the extension one column pass and one row pass of ``csrc/surface.hip``
+    (no host synchronisation); otherwise the separable plain-torch form above, the specification in code."""
+    if labels.dim() != 3 or labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise ValueError(f'labels must be integer [N, H, W], got {labels.dtype} {tuple(labels.shape)}')
+    cls = _sdf_classes(int(num_classes), classes)
+    n, h, w = labels.shape
+    _check_sdf_hw(h, w)
+    if n == 0:
+        return torch.zeros(0, len(cls), h, w, dtype=torch.int32 if squared else torch.float32, device=labels.device)
+    if not _native(labels):
+        s = _signed_distance_sq_torch(labels, int(num_classes), ignore_index, cls)
+        return s if squared else _phi_torch(s)
+    C = _ext.require()
+    s = torch.empty(n, len(cls), h, w, dtype=torch.int32, device=labels.device)
+    C.sdf_sq(labels.contiguous().long(), s, cls, int(num_classes), -1 if ignore_index is None else int(ignore_index))
+    if squared:
+        return s
+    phi = torch.empty(s.shape, dtype=torch.float32, device=s.device)
+    C.sdf_phi(s, phi)
+    return phi
+
+
 def surface_stats(preds, target, num_classes, ignore_index=None, nsd_tolerance=2.0, state=None, debug=False,
                   native=None):
     """Add the boundary statistics of one batch into ``state`` (see :func:`new_state`).

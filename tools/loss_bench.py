@@ -7,6 +7,10 @@ labels in each of its two passes and writes the gradient once.  From bytes alone
 (2 (L + T) + L) / (2 L + T) of the CE kernel's time: 1.67x at C = 2.
 
     python tools/loss_bench.py [--iters 20] [--out profiles/region_loss/loss_bench.json]
+
+``--mode boundary`` times the boundary (signed-distance) term instead, see :func:`boundary_mode`:
+
+    python tools/loss_bench.py --mode boundary [--iters 10] [--trials 5] [--out profiles/boundary_loss/boundary_bench.json]
 """
 import argparse
 import json
@@ -36,12 +40,130 @@ def timeit(fn, iters, warmup=5):
     return s.elapsed_time(e) / iters
 
 
+def _blob_labels(n, c, h, w, dev):
+    """A few discs per foreground class and image on background 0, two ignored rows: lesion-like targets."""
+    g = torch.Generator(device='cpu').manual_seed(0)
+    ys = torch.arange(h, device=dev).view(1, h, 1)
+    xs = torch.arange(w, device=dev).view(1, 1, w)
+    t = torch.zeros(n, h, w, dtype=torch.long, device=dev)
+    for k in range(1, c):
+        for _ in range(3):
+            cy = torch.randint(0, h, (n, 1, 1), generator=g).to(dev)
+            cx = torch.randint(0, w, (n, 1, 1), generator=g).to(dev)
+            r = torch.randint(4, max(5, min(h, w) // 5), (n, 1, 1), generator=g).to(dev)
+            t[(ys - cy) ** 2 + (xs - cx) ** 2 <= r * r] = k
+    t[:, :2] = 255
+    return t
+
+
+def _baseline_phi(t, c, classes):
+    """The signed distance map with the ops that predate ``signed_distance``: two ``edt_sq`` per class plus torch
+    select / sign / sqrt."""
+    from medical_segmentation_pytorch_amd.ops.surface import edt_sq
+    valid = (t != 255) & (t >= 0) & (t < c)
+    planes = []
+    for k in classes:
+        pos, neg = valid & (t == k), valid & (t != k)
+        live = (pos.flatten(1).any(1) & neg.flatten(1).any(1)).view(-1, 1, 1)
+        to_pos, to_neg = edt_sq(pos).float().sqrt(), edt_sq(neg).float().sqrt()
+        phi = torch.where(neg, to_pos, torch.zeros_like(to_pos)) - torch.where(pos, to_neg - 1.0,
+                                                                               torch.zeros_like(to_neg))
+        planes.append(torch.where(live, phi, torch.zeros_like(phi)))
+    return torch.stack(planes, 1), valid
+
+
+def boundary_mode(a):
+    """The boundary term at the bench shapes: signed-distance pass, loss forward and loss backward of the fused
+    path, each timed alone, against the same tensors from two ``edt_sq`` calls per class plus torch glue and an
+    autograd softmax * phi mean.  Every figure is the median of ``--trials`` windows of ``--iters`` calls; the
+    baseline's run-to-run spread (max - min over the trials) is reported with the ratio."""
+    from medical_segmentation_pytorch_amd.ops._ext import require
+    from medical_segmentation_pytorch_amd.ops.losses import boundary_loss
+    from medical_segmentation_pytorch_amd.ops.surface import signed_distance
+    C = require()
+    dev = torch.device('cuda', 0)
+    rows = []
+    for n, c, h, w in a.shapes or [(320, 2, 352, 352), (64, 4, 352, 352)]:
+        torch.manual_seed(0)
+        x = torch.randn(n, c, h, w, device=dev, requires_grad=True)
+        t = _blob_labels(n, c, h, w, dev)
+        classes = list(range(1, c))
+        s = signed_distance(t, c, 255, classes, squared=True)
+        part = torch.empty(C.boundary_blocks(n * h * w), 2, device=dev)
+        out = torch.empty(2, device=dev)
+        gup = torch.ones(1, device=dev)
+        grad = torch.empty_like(x)
+        xd = x.detach()
+
+        def base_loss(phi, valid):
+            p = torch.softmax(x, 1)[:, classes]
+            return (p * phi).sum() / (len(classes) * valid.sum().clamp_min(1))
+
+        phi_b, valid_b = _baseline_phi(t, c, classes)
+        same = bool(torch.equal(phi_b, signed_distance(t, c, 255, classes)))
+        x.grad = None
+        lb = base_loss(phi_b, valid_b)
+        lb.backward()
+        gb = x.grad.clone()
+        x.grad = None
+        lf = boundary_loss(x, t, 255, classes)
+        lf.backward()
+        agree = {'phi_bitwise_equal': same, 'loss_fused': lf.item(), 'loss_baseline': lb.item(),
+                 'grad_rel_l2': ((x.grad - gb).norm() / gb.norm()).item()}
+
+        def base_step():
+            x.grad = None
+            base_loss(phi_b, valid_b).backward()
+
+        def fused_step():
+            x.grad = None
+            boundary_loss(x, t, 255, classes).backward()
+
+        cases = {
+            'fused_sdf': lambda: C.sdf_sq(t, s, classes, c, 255),
+            'fused_fwd': lambda: C.boundary_fwd(xd, t, s, classes, part, out[:1], out[1:], 255),
+            'fused_bwd': lambda: C.boundary_grad(xd, t, s, classes, out[1:], gup, grad, 255),
+            'fused_all': fused_step,
+            'baseline_sdf': lambda: _baseline_phi(t, c, classes),
+            'baseline_loss_fwd_bwd': base_step,
+        }
+        ms = {k: [] for k in cases}
+        for _ in range(a.trials):                      # the variants alternate inside every trial
+            for k, fn in cases.items():
+                ms[k].append(timeit(fn, a.iters, warmup=2))
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        base = [ms['baseline_sdf'][i] + ms['baseline_loss_fwd_bwd'][i] for i in range(a.trials)]
+        base_med = sorted(base)[len(base) // 2]
+        row = {'shape': [n, c, h, w], 'classes': classes, 'ms_median': {k: round(v, 4) for k, v in med.items()},
+               'ms_trials': {k: [round(u, 4) for u in v] for k, v in ms.items()},
+               'baseline_total_ms': round(base_med, 4), 'baseline_spread_ms': round(max(base) - min(base), 4),
+               'fused_total_ms': round(med['fused_all'], 4),
+               'baseline_over_fused': round(base_med / med['fused_all'], 2),
+               'sdf_baseline_over_fused': round(med['baseline_sdf'] / med['fused_sdf'], 2), 'agreement': agree}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del x, t, s, grad, phi_b, valid_b, gb
+        torch.cuda.empty_cache()
+    out_path = a.out or os.path.join('profiles', 'boundary_loss', 'boundary_bench.json')
+    os.makedirs(os.path.dirname(out_path) or '.', exist_ok=True)
+    with open(out_path, 'w') as f:
+        json.dump({'device': torch.cuda.get_device_name(0), 'iters': a.iters, 'trials': a.trials,
+                   'note': 'ms per call (HIP events); fused_all = signed distance + forward + backward through '
+                           'autograd; baseline = 2 edt_sq per class + torch glue, then autograd softmax * phi',
+                   'rows': rows}, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--mode', choices=['region', 'boundary'], default='region')
     ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--trials', type=int, default=5, help='boundary mode: timed windows per variant')
     ap.add_argument('--shapes', type=int, nargs=4, action='append', metavar=('N', 'C', 'H', 'W'))
-    ap.add_argument('--out', default=os.path.join('profiles', 'region_loss', 'loss_bench.json'))
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.mode == 'boundary':
+        return boundary_mode(a)
+    a.out = a.out or os.path.join('profiles', 'region_loss', 'loss_bench.json')
     dev = torch.device('cuda', 0)
     rows = []
     for n, c, h, w in a.shapes or [(320, 2, 352, 352), (32, 4, 352, 352)]:
