@@ -1000,6 +1000,94 @@ void boundary_grad_t(const at::Tensor& logits, const at::Tensor& target, const a
                 f32(grad), N, C, HW, (int)ignore_index, cur_stream());
 }
 
+// ---- segmented radix sort (sort.hip) and the Lovasz-softmax loss on it (lovasz.hip)
+inline unsigned* u32(const at::Tensor& t) { return reinterpret_cast<unsigned*>(t.data_ptr()); }
+
+static void sort_ws_check(const at::Tensor& table, const at::Tensor& dtot, int64_t Q, int64_t P) {
+  CHECK_I32(table); CHECK_I32(dtot);
+  TORCH_CHECK(Q >= 1 && Q <= 65535, "sort: rows must be in [1, 65535], got ", Q);
+  TORCH_CHECK(P >= 1 && P < (int64_t(1) << 31), "sort: row length must be in [1, 2^31), got ", P);
+  const int64_t nblk = (P + sort_tile() - 1) / sort_tile();
+  TORCH_CHECK(table.numel() >= Q * sort_bins() * nblk, "table must be [Q, sort_bins, ceil(P / sort_tile)]");
+  TORCH_CHECK(dtot.numel() >= Q * sort_bins(), "dtot must be [Q, sort_bins]");
+}
+
+// keys fp32 [Q, P] -> values fp32 [Q, P], index int32 [Q, P]; tmp int32 [2, Q, P]
+void sort_segments_t(const at::Tensor& keys, const at::Tensor& values, const at::Tensor& index, const at::Tensor& tmp,
+                     const at::Tensor& table, const at::Tensor& dtot) {
+  CHECK_F32(keys); CHECK_F32(values); CHECK_I32(index); CHECK_I32(tmp);
+  TORCH_CHECK(keys.dim() == 2, "keys must be [Q, P]");
+  const int64_t Q = keys.size(0), P = keys.size(1);
+  sort_ws_check(table, dtot, Q, P);
+  TORCH_CHECK(values.numel() == Q * P && index.numel() == Q * P && tmp.numel() == 2 * Q * P,
+              "values, index [Q, P]; tmp [2, Q, P]");
+  sort_segments(u32(keys), nullptr, u32(values), u32(index), u32(tmp), u32(tmp) + Q * P, u32(table), u32(dtot), (int)Q,
+                (long)P, cur_stream());
+}
+
+struct LovaszDims { int N, C, S; long HW, P; int nblk; };
+
+static LovaszDims lovasz_check(const at::Tensor& logits, const at::Tensor& target, bool per_image) {
+  CHECK_F32(logits); CHECK_I64(target);
+  TORCH_CHECK(logits.dim() == 4, "logits must be NCHW");
+  const int64_t N = logits.size(0), C = logits.size(1), HW = logits.size(2) * logits.size(3);
+  TORCH_CHECK(C >= 2 && C <= lovasz_max_classes(), "lovasz loss: num_class must be in [2, ", lovasz_max_classes(),
+              "], got ", C);
+  TORCH_CHECK(N >= 1 && N <= 65535 && HW >= 1, "lovasz loss: batch must be in [1, 65535]");
+  TORCH_CHECK(target.numel() == N * HW, "target must be [N, H, W]");
+  const int64_t P = per_image ? HW : N * HW;
+  TORCH_CHECK(P < (int64_t(1) << 31), "lovasz loss: segment length must be < 2^31, got ", P);
+  return {(int)N, (int)C, per_image ? (int)N : 1, (long)HW, (long)P, (int)((P + lovasz_tile() - 1) / lovasz_tile())};
+}
+
+// one chunk of classes [c_lo, c_lo + CK): keys, sort, coefficients.  ws int32 [4, S * CK, P]
+void lovasz_chunk_t(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& ws, const at::Tensor& table,
+                    const at::Tensor& dtot, const at::Tensor& cnt, const at::Tensor& gtot, const at::Tensor& part,
+                    const at::Tensor& coef, int64_t ignore_index, bool per_image, int64_t c_lo, int64_t CK) {
+  const LovaszDims d = lovasz_check(logits, target, per_image);
+  CHECK_I32(ws); CHECK_I32(cnt); CHECK_I32(gtot); CHECK_F32(part); CHECK_F32(coef);
+  TORCH_CHECK(c_lo >= 0 && CK >= 1 && c_lo + CK <= d.C, "class chunk [c_lo, c_lo + CK) must lie in [0, C)");
+  const int64_t Q = (int64_t)d.S * CK, R = (int64_t)d.S * d.C;
+  sort_ws_check(table, dtot, Q, d.P);
+  TORCH_CHECK(ws.numel() == 4 * Q * d.P, "ws must be [4, S * CK, P]");
+  TORCH_CHECK(cnt.numel() == R * d.nblk && part.numel() == R * d.nblk && gtot.numel() == R,
+              "cnt, part [S * C, blocks]; gtot [S * C]");
+  TORCH_CHECK(coef.numel() == logits.numel(), "coef must be shaped like logits");
+  auto s = cur_stream();
+  unsigned *k0 = u32(ws), *p0 = k0 + Q * d.P, *k1 = p0 + Q * d.P, *p1 = k1 + Q * d.P;
+  lovasz_keys(f32(logits), target.data_ptr<int64_t>(), reinterpret_cast<float*>(k0), p0, d.N, d.C, d.HW,
+              (int)ignore_index, per_image ? 1 : 0, (int)c_lo, (int)CK, s);
+  // passes alternate tmp (k1, p1) and out (k0, p0): the first pass reads k0 / p0, the last one writes them
+  sort_segments(k0, p0, k0, p0, k1, p1, u32(table), u32(dtot), (int)Q, d.P, s);
+  lovasz_coef(reinterpret_cast<const float*>(k0), p0, u32(cnt), u32(gtot), f32(part), f32(coef), d.N, d.C, d.HW,
+              per_image ? 1 : 0, (int)c_lo, (int)CK, s);
+}
+
+void lovasz_finalize_t(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& part,
+                       const at::Tensor& gtot, const at::Tensor& rowloss, const at::Tensor& scale,
+                       const at::Tensor& loss, bool per_image, int64_t c0) {
+  const LovaszDims d = lovasz_check(logits, target, per_image);
+  CHECK_F32(part); CHECK_I32(gtot); CHECK_F32(rowloss); CHECK_F32(scale); CHECK_F32(loss);
+  const int64_t R = (int64_t)d.S * d.C;
+  TORCH_CHECK(part.numel() == R * d.nblk && gtot.numel() == R && rowloss.numel() == R && scale.numel() == R,
+              "part [S * C, blocks]; gtot, rowloss, scale [S * C]");
+  TORCH_CHECK(loss.numel() == 1, "loss must be [1]");
+  TORCH_CHECK(c0 == 0 || c0 == 1, "c0: first counted class, 0 or 1");
+  lovasz_finalize(f32(part), u32(gtot), f32(rowloss), f32(scale), f32(loss), d.N, d.C, d.HW, per_image ? 1 : 0,
+                  (int)c0, cur_stream());
+}
+
+void lovasz_grad_t(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& coef,
+                   const at::Tensor& scale, const at::Tensor& gup, const at::Tensor& grad, int64_t ignore_index,
+                   bool per_image) {
+  const LovaszDims d = lovasz_check(logits, target, per_image);
+  CHECK_F32(coef); CHECK_F32(scale); CHECK_F32(gup); CHECK_F32(grad);
+  TORCH_CHECK(coef.numel() == logits.numel() && grad.numel() == logits.numel(), "coef, grad like logits");
+  TORCH_CHECK(scale.numel() == (int64_t)d.S * d.C && gup.numel() == 1, "scale [S * C], gup [1]");
+  lovasz_grad(f32(logits), target.data_ptr<int64_t>(), f32(coef), f32(scale), f32(gup), f32(grad), d.N, d.C, d.HW,
+              (int)ignore_index, per_image ? 1 : 0, cur_stream());
+}
+
 // ---- connected components (components.hip)
 static void cc_planes_check(const at::Tensor& lab, const at::Tensor& root, const at::Tensor& area,
                             const at::Tensor& aux) {
@@ -1682,6 +1770,15 @@ PYBIND11_MODULE(_C, m) {
   m.def("boundary_blocks", &boundary_blocks_t);
   m.def("boundary_fwd", &boundary_fwd_t);
   m.def("boundary_grad", &boundary_grad_t);
+  m.def("sort_tile", []() { return sort_tile(); });
+  m.def("sort_bins", []() { return sort_bins(); });
+  m.def("sort_passes", []() { return sort_passes(); });
+  m.def("sort_segments", &sort_segments_t);
+  m.def("lovasz_max_classes", []() { return lovasz_max_classes(); });
+  m.def("lovasz_tile", []() { return lovasz_tile(); });
+  m.def("lovasz_chunk", &lovasz_chunk_t);
+  m.def("lovasz_finalize", &lovasz_finalize_t);
+  m.def("lovasz_grad", &lovasz_grad_t);
   m.def("cc_label", &cc_label_t, py::arg("lab"), py::arg("root"), py::arg("area"), py::arg("aux"), py::arg("err"),
         py::arg("half") = 0, py::arg("connectivity") = 8, py::arg("mode") = 0);
   m.def("cc_rank", &cc_rank_t);

@@ -279,6 +279,31 @@ void boundary_grad(const float* logits, const int64_t* target, const int32_t* sd
                    const float* norm, const float* gup, float* grad, int N, int C, long HW, int ignore_index,
                    hipStream_t s);
 
+// sort.hip: stable segmented radix sort, descending by the uint32 bit pattern of the key, of Q rows of P keys
+// with a 32-bit payload (payload == nullptr: the key's position in its row).  out_* and tmp_* are [Q][P];
+// table [Q][sort_bins()][cdiv(P, sort_tile())] and dtot [Q][sort_bins()] are workspace.  Q <= 65535, P < 2^31.
+int sort_tile();
+int sort_bins();
+int sort_passes();
+void sort_segments(const unsigned* keys, const unsigned* payload, unsigned* out_keys, unsigned* out_payload,
+                   unsigned* tmp_keys, unsigned* tmp_payload, unsigned* table, unsigned* dtot, int Q, long P,
+                   hipStream_t s);
+
+// lovasz.hip: Lovasz-softmax on the sort above.  Segments: the batch (per_image = 0; S = 1, P = N * HW) or the
+// images (S = N, P = HW); classes [c_lo, c_lo + CK) per call, chunk rows q = s * CK + (c - c_lo), global rows
+// s * C + c.  keys / pay [S * CK][P]; cnt, part [S * C][cdiv(P, lovasz_tile())]; gtot, rowloss, scale [S * C];
+// coef [N][C][HW] = sign(p - y) g (unscaled); loss [1]; gup device scalar.
+int lovasz_max_classes();
+int lovasz_tile();
+void lovasz_keys(const float* logits, const int64_t* target, float* keys, unsigned* pay, int N, int C, long HW,
+                 int ignore_index, int per_image, int c_lo, int CK, hipStream_t s);
+void lovasz_coef(const float* keys, const unsigned* pay, unsigned* cnt, unsigned* gtot, float* part, float* coef,
+                 int N, int C, long HW, int per_image, int c_lo, int CK, hipStream_t s);
+void lovasz_finalize(const float* part, const unsigned* gtot, float* rowloss, float* scale, float* loss, int N, int C,
+                     long HW, int per_image, int c0, hipStream_t s);
+void lovasz_grad(const float* logits, const int64_t* target, const float* coef, const float* scale, const float* gup,
+                 float* grad, int N, int C, long HW, int ignore_index, int per_image, hipStream_t s);
+
 // optim.hip  (flat fp32 buffers; hyper = device fp32 array, see optim.hip for the layout)
 void adam_step(float* p, const float* g, float* m, float* v, const float* hyper, long n, int adamw,
                const float* amp, hipStream_t s);

@@ -90,6 +90,9 @@ class BaseConfig:
         self.loss_boundary_weight = 0.01      # >= 0
         self.boundary_ramp_epochs = 0         # weight * min(1, (epoch + 1) / R) for R > 0
         self.boundary_include_background = False   # True: class 0 gets a distance map as well
+        # Lovasz-softmax term of the '*lovasz_softmax' loss types (core.loss.LovaszSoftmaxLoss): weighted by
+        # loss_region_weight, class 0 left out with dice_ignore_background
+        self.lovasz_per_image = False  # True: sort and average per image; False: over the whole batch
 
         # Scheduler
         self.lr_policy = 'cos_warmup'

@@ -72,7 +72,9 @@ def get_parser():
                                              'ce_tversky', 'focal_dice', 'focal_tversky', 'boundary', 'ce_boundary',
                                              'focal_boundary', 'dice_boundary', 'tversky_boundary',
                                              'ce_dice_boundary', 'ce_tversky_boundary', 'focal_dice_boundary',
-                                             'focal_tversky_boundary'])
+                                             'focal_tversky_boundary', 'lovasz_softmax', 'ce_lovasz_softmax',
+                                             'focal_lovasz_softmax'])
+    _flag(p, 'lovasz_per_image', action='store_true')
     _flag(p, 'loss_boundary_weight', type=float)
     _flag(p, 'boundary_ramp_epochs', type=int)
     _flag(p, 'boundary_include_background', action='store_true')

@@ -6,7 +6,8 @@ semantics.  Added (north star): ``'bce_dice'`` for ``num_cl
 softmax heads (``num_class >= 2``) the overlap / focal family of :class:`RegionLoss`: ``dice``,
 ``tversky``, ``focal``, ``ce_dice``, ``ce_tversky``, ``focal_dice``, ``focal_tversky``.  Each of those, and the
 empty base, can carry the boundary (signed-distance) term of :class:`BoundaryLoss`: ``boundary``,
-``ce_boundary``, ``ce_dice_boundary`` and so on.
+``ce_boundary``, ``ce_dice_boundary`` and so on.  :class:`LovaszSoftmaxLoss` adds the Lovasz-softmax surrogate of the
+Jaccard index: ``lovasz_softmax``, ``ce_lovasz_softmax``, ``focal_lovasz_softmax``.
 """
 from __future__ import annotations
 
@@ -207,10 +208,80 @@ class BoundaryLoss(nn.Module):
         return loss if self.base is None else self.base(logits, labels) + loss
 
 
+class LovaszSoftmaxLoss(nn.Module):
+    """``base(logits, labels) + weight * L`` for softmax heads: ``base`` an optional pixel-only :class:`RegionLoss`
+    (``region=None``), ``L`` the Lovasz-softmax loss of Berman et al. (CVPR 2018), the convex surrogate of the
+    Jaccard index, over the classes present in a segment.
+
+    With ``p = softmax(logits)`` and the :class:`RegionLoss` validity rule, a segment is the whole batch
+    (``per_image=False``, as in Berman's code) or one image.  For a segment ``s`` and class ``c``, over the valid
+    pixels of ``s``: ``y = [label == c]``, ``e = |y - p_c|``, ``G = sum y``; the class is *present* iff ``G > 0``.
+    The pixels are sorted by ``e`` descending, ties in ascending pixel index (raster order, ``n`` major in batch
+    mode).  Along that order, with ``F_i`` the number of ``y = 1`` among the first ``i + 1`` pixels and
+    ``B_i = i + 1 - F_i``: ``I_i = G - F_i``, ``U_i = G + B_i``, ``J_i = 1 - I_i / U_i`` and
+    ``g_i = J_i - J_{i-1}`` (``J_{-1} = 0``), i.e. ``g_i = 1 / U_i`` where ``y_i = 1`` and
+    ``I_i / (U_i (U_i - 1))`` where ``y_i = 0``.  ``L_sc = sum_i e_i g_i`` with ``g`` a constant under
+    differentiation; ``L_s`` is the mean of ``L_sc`` over the present classes (class 0 left out with
+    ``ignore_background``; 0 if none is left) and ``L = mean_s L_s``: an image without a valid pixel adds 0 and
+    still counts.  No valid pixel at all: ``L = 0`` with zero gradient.
+
+    Only the 'present' mode, no class weights.  The batch-mode sort is over the rank's own micro-batch: nothing is
+    exchanged across DDP ranks or accumulation micro-batches, the same semantics as ``ce``.  On a ROCm device with
+    the HIP extension ``L`` is ``ops.losses.lovasz_softmax`` (fused, deterministic, graph-capturable); elsewhere
+    the plain-torch form below, in the input's floating dtype: invalid pixels carry the error 0 instead of being
+    compacted (everything at ``e = 0`` contributes nothing), so there is no boolean indexing and no host sync."""
+
+    def __init__(self, base=None, weight=1.0, per_image=False, ignore_index=255, ignore_background=False):
+        super().__init__()
+        if base is not None and not (isinstance(base, RegionLoss) and base.region is None):
+            raise ValueError('LovaszSoftmaxLoss: base must be a pixel-only RegionLoss (region=None) or None, got '
+                             f'{type(base).__name__}')
+        self.base, self.weight, self.per_image = base, float(weight), bool(per_image)
+        self.ignore_index, self.ignore_background = ignore_index, bool(ignore_background)
+
+    def lovasz_term(self, logits, labels):
+        if logits.dim() == 4 and logits.shape[1] == 1:
+            raise ValueError('LovaszSoftmaxLoss needs a softmax head: num_class must be >= 2, got 1')
+        if _fused_ok(logits):
+            from ..ops.losses import lovasz_softmax
+            return lovasz_softmax(logits.float(), labels, self.ignore_index, self.per_image, self.ignore_background)
+        return self.plain_term(logits, labels)
+
+    def plain_term(self, logits, labels):
+        """The specification in plain torch (``torch.sort``), on any device."""
+        x = logits if logits.dtype in (torch.float32, torch.float64) else logits.float()
+        N, C = x.shape[:2]
+        valid = (labels != self.ignore_index) & (labels >= 0) & (labels < C)
+        vf = valid.unsqueeze(1).to(x.dtype)
+        y = F.one_hot(torch.where(valid, labels, torch.zeros_like(labels)), C).movedim(-1, 1).to(x.dtype) * vf
+        e = (y - F.softmax(x, 1)).abs() * vf                       # 0 at invalid pixels
+        if self.per_image:                                         # rows [S, C, P]
+            e, y = e.flatten(2), y.flatten(2)
+        else:
+            e, y = e.movedim(1, 0).reshape(1, C, -1), y.movedim(1, 0).reshape(1, C, -1)
+        es, order = torch.sort(e, dim=-1, descending=True, stable=True)
+        ys = y.detach().gather(-1, order).long()
+        G = ys.sum(-1, keepdim=True)
+        Fi = ys.cumsum(-1)
+        U = G + torch.arange(1, e.shape[-1] + 1, device=x.device) - Fi           # G + B_i
+        g = torch.where(ys > 0, 1 / U.clamp_min(1).to(x.dtype),
+                        (G - Fi).to(x.dtype) / (U * (U - 1)).clamp_min(1).to(x.dtype))
+        present = (G[..., 0] > 0).to(x.dtype)                      # [S, C]
+        if self.ignore_background:
+            present = present * (torch.arange(C, device=x.device) > 0).to(x.dtype)
+        Lsc = (es * g).sum(-1) * present
+        return (Lsc.sum(1) / present.sum(1).clamp_min(1)).mean()
+
+    def forward(self, logits, labels):
+        loss = self.weight * self.lovasz_term(logits, labels)
+        return loss if self.base is None else self.base(logits, labels) + loss
+
+
 _PIXEL_TERMS, _REGION_TERMS = ('ce', 'focal'), ('dice', 'tversky')
 REGION_LOSS_TYPES = ('dice', 'tversky', 'focal', 'ce_dice', 'ce_tversky', 'focal_dice', 'focal_tversky')
 BOUNDARY_LOSS_TYPES = ('boundary', 'ce_boundary', 'focal_boundary', 'dice_boundary', 'tversky_boundary',
                        'ce_dice_boundary', 'ce_tversky_boundary', 'focal_dice_boundary', 'focal_tversky_boundary')
+LOVASZ_LOSS_TYPES = ('lovasz_softmax', 'ce_lovasz_softmax', 'focal_lovasz_softmax')
 
 
 def _region_loss_of(terms, config, weights):
@@ -252,6 +323,14 @@ def get_loss_fn(config, device):
         return BoundaryLoss(base, weight=config.loss_boundary_weight, ramp_epochs=config.boundary_ramp_epochs,
                             ignore_index=config.ignore_index, include_background=config.boundary_include_background,
                             device=device)
+    if lt in LOVASZ_LOSS_TYPES:
+        if not multi:
+            raise ValueError(f"loss_type '{lt}' needs a softmax head (the Lovasz-softmax errors are taken on the "
+                             f"softmax), but num_class = {config.num_class}")
+        pixel = lt[:-len('_lovasz_softmax')] if lt != 'lovasz_softmax' else None
+        base = _region_loss_of([pixel], config, weights) if pixel else None
+        return LovaszSoftmaxLoss(base, weight=config.loss_region_weight, per_image=config.lovasz_per_image,
+                                 ignore_index=config.ignore_index, ignore_background=config.dice_ignore_background)
     raise NotImplementedError(f'Unsupport loss type: {lt}')
 
 

@@ -21,6 +21,8 @@
 * :func:`boundary_loss`: the softmax integrated against the signed distance map of the labels (the
   plain-torch form is ``core.loss.BoundaryLoss``); the map comes from ``csrc/surface.hip`` inside the
   same call and is kept as int32 squared distances for the gradient pass.
+* :func:`lovasz_softmax`: the Lovasz-softmax loss (the plain-torch form is ``core.loss.LovaszSoftmaxLoss``) on
+  the segmented radix sort of ``csrc/sort.hip``; the kernels are ``csrc/lovasz.hip``.
 """
 from __future__ import annotations
 
@@ -230,6 +232,83 @@ class _Boundary(torch.autograd.Function):
         require().boundary_grad(x, t, s, classes, out[1:], g.detach().float().reshape(1).contiguous(), grad,
                                 ignore_index)
         return grad, None, None, None
+
+
+LOVASZ_WS_BYTES = 2 << 30     # bound of the sort workspace of one class chunk
+
+
+def lovasz_chunk_classes(n, c, hw, per_image):
+    """Classes sorted per chunk: as many as keep ``16 * CK * N * H * W`` bytes under ``LOVASZ_WS_BYTES`` (at least
+    one), and the chunk's rows ``S * CK`` within the launch grid."""
+    ck = max(1, min(c, LOVASZ_WS_BYTES // (16 * n * hw)))
+    return max(1, min(ck, 65535 // n)) if per_image else ck
+
+
+class _Lovasz(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, per_image, c0):
+        C = require()
+        x = logits.contiguous().float()
+        t = target.contiguous().long()
+        n, c, h, w = x.shape
+        dev = x.device
+        S, P = (n, h * w) if per_image else (1, n * h * w)
+        nblk = -(-P // C.lovasz_tile())
+        ck = lovasz_chunk_classes(n, c, h * w, per_image)
+        i32 = dict(dtype=torch.int32, device=dev)
+        ws = torch.empty(4 * S * ck * P, **i32)                     # keys and payload, in and out of a pass
+        table = torch.empty(S * ck, C.sort_bins(), -(-P // C.sort_tile()), **i32)
+        dtot = torch.empty(S * ck, C.sort_bins(), **i32)
+        cnt, gtot = torch.empty(S * c, nblk, **i32), torch.empty(S * c, **i32)
+        part = torch.empty(S * c, nblk, dtype=torch.float32, device=dev)
+        coef = torch.empty_like(x)
+        out = torch.empty(2 * S * c + 1, dtype=torch.float32, device=dev)   # row loss, scale, loss
+        for lo in range(0, c, ck):
+            k = min(ck, c - lo)
+            C.lovasz_chunk(x, t, ws[:4 * S * k * P], table, dtot, cnt, gtot, part, coef, ignore_index, per_image,
+                           lo, k)
+        scale, loss = out[S * c:2 * S * c], out[2 * S * c:]
+        C.lovasz_finalize(x, t, part, gtot, out[:S * c], scale, loss, per_image, c0)
+        ctx.save_for_backward(x, t, coef, scale)
+        ctx.args = (ignore_index, per_image)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t, coef, scale = ctx.saved_tensors
+        grad = torch.empty_like(x)
+        require().lovasz_grad(x, t, coef, scale, g.detach().float().reshape(1).contiguous(), grad, *ctx.args)
+        return grad, None, None, None, None
+
+
+def lovasz_softmax(logits, target, ignore_index=255, per_image=False, ignore_background=False):
+    """Lovasz-softmax loss (Berman et al., CVPR 2018), 'present' classes, on fp32 NCHW logits and int64
+    ``[N, H, W]`` labels; the plain-torch form and the definition are ``core.loss.LovaszSoftmaxLoss``.
+
+    Per segment (the batch, or each image with ``per_image``) and class the errors ``|y - p_c|`` of all pixels
+    (0 at invalid ones) are sorted descending, ties in ascending pixel index, by ``csrc/sort.hip``; one pass along
+    the sorted order turns the running integer counts into the Lovasz gradient ``g``, sums ``e g`` and scatters
+    ``sign(p - y) g`` back to pixel order; a one-block finalize takes the mean over the present classes and the
+    segments.  Backward is one pass that recomputes the softmax.  No float atomics, no host read: bitwise
+    repeatable and graph-capturable.  The batch-mode sort is over the rank's own micro-batch: nothing is exchanged
+    across DDP ranks or accumulation micro-batches, the same semantics as ``cross_entropy``.
+
+    ``C <= 64``, segment length ``< 2^31``.  Classes are sorted in chunks of ``CK = lovasz_chunk_classes(...)``;
+    peak workspace in bytes, with ``V = N * H * W``, ``T = sort_tile()``, rows ``R = S * C`` and ``Rk = S * CK``:
+    ``16 * CK * V`` (keys and payload, in and out of a pass) ``+ 4 * 256 * Rk * (ceil(P / T) + 1)`` (digit table)
+    ``+ 8 * R * ceil(P / T) + 12 * R`` (counts, partials, per-row results) ``+ 4 * C * V`` (the coefficient tensor
+    kept for backward)."""
+    if logits.dim() != 4 or target.shape != logits.shape[:1] + logits.shape[2:]:
+        raise ValueError(f'lovasz_softmax: logits [N, C, H, W] and target [N, H, W], got {tuple(logits.shape)} and '
+                         f'{tuple(target.shape)}')
+    n, c, h, w = logits.shape
+    if c == 1:
+        raise ValueError('lovasz_softmax needs a softmax head: num_class must be >= 2, got 1')
+    if c > 64:
+        raise RuntimeError(f'lovasz loss: num_class must be in [2, 64], got {c}')
+    if (h * w if per_image else n * h * w) >= 1 << 31:
+        raise RuntimeError(f'lovasz loss: segment length must be < 2^31, got {h * w if per_image else n * h * w}')
+    return _Lovasz.apply(logits, target, int(ignore_index), bool(per_image), 1 if ignore_background else 0)
 
 
 def boundary_loss(logits, target, ignore_index=255, classes=None):

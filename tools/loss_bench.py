@@ -11,6 +11,10 @@ labels in each of its two passes and writes the gradient once.  From bytes alone
 ``--mode boundary`` times the boundary (signed-distance) term instead, see :func:`boundary_mode`:
 
     python tools/loss_bench.py --mode boundary [--iters 10] [--trials 5] [--out profiles/boundary_loss/boundary_bench.json]
+
+``--mode lovasz`` times the Lovasz-softmax loss against its plain-torch form and CE, see :func:`lovasz_mode`:
+
+    python tools/loss_bench.py --mode lovasz [--iters 5] [--trials 3] [--out profiles/lovasz_loss/lovasz_bench.json]
 """
 import argparse
 import json
@@ -153,9 +157,82 @@ def boundary_mode(a):
                    'rows': rows}, f, indent=1)
 
 
+def lovasz_mode(a):
+    """The Lovasz-softmax loss at the bench shapes, both ``per_image`` settings: forward + backward of the fused
+    path (keys, 4-pass radix sort, coefficients, finalize, gradient) against the plain-torch form of
+    ``LovaszSoftmaxLoss`` on the same device (``torch.sort``) and against ``cross_entropy``; the sort alone
+    (``sort_segments`` on the same number of keys) is timed apart.  Every figure is the median of ``--trials``
+    windows of ``--iters`` calls.  Bytes are the compulsory traffic of the fused path: per class and pixel
+    ``passes * 20`` (key read by the histogram, key + payload read and written by the scatter) + 8 written by the key
+    pass + 4 (payload) read by the count pass + 8 read by the coefficient pass + 4 coefficient written and 4 read
+    again, plus logits and labels read by the key and gradient passes and the gradient written."""
+    from medical_segmentation_pytorch_amd.core.loss import LovaszSoftmaxLoss
+    from medical_segmentation_pytorch_amd.ops._ext import require
+    from medical_segmentation_pytorch_amd.ops.losses import lovasz_softmax
+    from medical_segmentation_pytorch_amd.ops.sort import sort_segments
+    passes = require().sort_passes()
+    dev = torch.device('cuda', 0)
+    rows = []
+    for n, c, h, w in a.shapes or [(320, 2, 352, 352), (32, 4, 352, 352)]:
+        torch.manual_seed(0)
+        x = torch.randn(n, c, h, w, device=dev, requires_grad=True)
+        t = _blob_labels(n, c, h, w, dev)
+        V = n * h * w
+        nbytes = c * V * (passes * 20 + 28) + 2 * (c * V * 4 + V * 8) + c * V * 4
+
+        def step(fn):
+            x.grad = None
+            fn().backward()
+
+        for per_image in (False, True):
+            plain = LovaszSoftmaxLoss(per_image=per_image)
+            keys = torch.rand((n * c, h * w) if per_image else (c, V), device=dev)
+            x.grad = None
+            lf = lovasz_softmax(x, t, 255, per_image)
+            lf.backward()
+            gf = x.grad.clone()
+            x.grad = None
+            lp = plain.plain_term(x, t)
+            lp.backward()
+            agree = {'loss_fused': lf.item(), 'loss_plain': lp.item(),
+                     'grad_rel_l2': ((gf - x.grad).norm() / x.grad.norm()).item()}
+            del gf
+            cases = {
+                'fused': lambda: step(lambda: lovasz_softmax(x, t, 255, per_image)),
+                'fused_fwd': lambda: lovasz_softmax(x.detach(), t, 255, per_image),
+                'sort_only': lambda: sort_segments(keys),
+                'torch_sort_only': lambda: torch.sort(keys, dim=1, descending=True, stable=True),
+                'plain_torch': lambda: step(lambda: plain.plain_term(x, t)),
+                'ce': lambda: step(lambda: cross_entropy(x, t)),
+            }
+            ms = {k: [] for k in cases}
+            for _ in range(a.trials):                  # the variants alternate inside every trial
+                for k, fn in cases.items():
+                    ms[k].append(timeit(fn, a.iters, warmup=1))
+            med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+            row = {'shape': [n, c, h, w], 'per_image': per_image, 'ms_median': {k: round(v, 4) for k, v in med.items()},
+                   'ms_trials': {k: [round(u, 4) for u in v] for k, v in ms.items()},
+                   'plain_over_fused': round(med['plain_torch'] / med['fused'], 2),
+                   'fused_over_ce': round(med['fused'] / med['ce'], 2),
+                   'torch_sort_over_sort': round(med['torch_sort_only'] / med['sort_only'], 2),
+                   'bytes': nbytes, 'tb_per_s': round(nbytes / med['fused'] / 1e9, 3), 'agreement': agree}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del keys
+            torch.cuda.empty_cache()
+        del x, t
+        torch.cuda.empty_cache()
+    out_path = a.out or os.path.join('profiles', 'lovasz_loss', 'lovasz_bench.json')
+    os.makedirs(os.path.dirname(out_path) or '.', exist_ok=True)
+    with open(out_path, 'w') as f:
+        json.dump({'device': torch.cuda.get_device_name(0), 'iters': a.iters, 'trials': a.trials,
+                   'note': 'ms per call (HIP events); fused / plain_torch / ce = forward + backward through autograd',
+                   'rows': rows}, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--mode', choices=['region', 'boundary'], default='region')
+    ap.add_argument('--mode', choices=['region', 'boundary', 'lovasz'], default='region')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--trials', type=int, default=5, help='boundary mode: timed windows per variant')
     ap.add_argument('--shapes', type=int, nargs=4, action='append', metavar=('N', 'C', 'H', 'W'))
@@ -163,6 +240,8 @@ def main():
     a = ap.parse_args()
     if a.mode == 'boundary':
         return boundary_mode(a)
+    if a.mode == 'lovasz':
+        return lovasz_mode(a)
     a.out = a.out or os.path.join('profiles', 'region_loss', 'loss_bench.json')
     dev = torch.device('cuda', 0)
     rows = []
