@@ -850,9 +850,58 @@ void confmat_update_t(const at::Tensor& logits, const at::Tensor& target, const 
                  cur_stream());
 }
 
-// ---- boundary metrics (surface.hip)
 #define CHECK_U8(t) CHECK_DEV(t); TORCH_CHECK((t).scalar_type() == at::kByte, #t " must be uint8")
 #define CHECK_I32(t) CHECK_DEV(t); TORCH_CHECK((t).scalar_type() == at::kInt, #t " must be int32")
+
+// ---- calibration (calibration.hip)
+struct CalibDims { int N, C; long HW; };
+static CalibDims calib_dims(const at::Tensor& logits, const at::Tensor& target, int64_t cmin) {
+  TORCH_CHECK(logits.dim() == 4, "logits must be NCHW");
+  const int64_t N = logits.size(0), C = logits.size(1), HW = logits.size(2) * logits.size(3);
+  TORCH_CHECK(C >= cmin && C <= kCalibMaxClasses, "calibration: the class dimension must be in [", cmin, ", ",
+              kCalibMaxClasses, "], got ", C);
+  TORCH_CHECK(N >= 1 && N <= 2147483647LL && HW >= 1, "logits must be a non-empty [N, C, H, W]");
+  if (target.defined()) TORCH_CHECK(target.numel() == N * HW, "target must be [N, H, W]");
+  return {(int)N, (int)C, (long)HW};
+}
+
+void calib_stats_t(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& ints, const at::Tensor& sums,
+                   const at::Tensor& part, double T, int64_t ignore_index, int64_t bins) {
+  CHECK_F32(logits); CHECK_I64(target); CHECK_I64(ints); CHECK_F64(sums); CHECK_F64(part);
+  const CalibDims d = calib_dims(logits, target, 2);
+  TORCH_CHECK(bins >= 1 && bins <= kCalibMaxBins, "calibration bins must be in [1, ", kCalibMaxBins, "], got ", bins);
+  TORCH_CHECK(T > 0 && std::isfinite(T) && (float)T > 0.f && std::isfinite((float)T),
+              "temperature must be a finite number > 0, got ", T);
+  TORCH_CHECK(ints.numel() == 2 * bins && sums.numel() == bins + 2, "state: ints [2, bins], sums [bins + 2]");
+  TORCH_CHECK(part.numel() >= (int64_t)calib_blocks((long)d.N * d.HW) * (bins + 2), "part is too small");
+  calib_stats(f32(logits), target.data_ptr<int64_t>(), ints.data_ptr<int64_t>(), sums.data_ptr<double>(),
+              part.data_ptr<double>(), d.N, d.C, d.HW, (int)ignore_index, (int)bins, (float)T, cur_stream());
+}
+
+void calib_nll_grid_t(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& betas,
+                      const at::Tensor& sums, const at::Tensor& part, int64_t ignore_index) {
+  CHECK_F32(logits); CHECK_I64(target); CHECK_F32(betas); CHECK_F64(sums); CHECK_F64(part);
+  const CalibDims d = calib_dims(logits, target, 2);
+  const int64_t K = sums.numel();
+  TORCH_CHECK(K >= 1 && K <= kCalibMaxK, "nll_grid: K must be in [1, ", kCalibMaxK, "], got ", K);
+  TORCH_CHECK(betas.numel() == kCalibMaxK, "betas must be padded to ", kCalibMaxK, " values");
+  TORCH_CHECK(part.numel() >= (int64_t)calib_blocks((long)d.N * d.HW) * K, "part is too small");
+  calib_nll_grid(f32(logits), target.data_ptr<int64_t>(), f32(betas), sums.data_ptr<double>(), part.data_ptr<double>(),
+                 d.N, d.C, d.HW, (int)ignore_index, (int)K, cur_stream());
+}
+
+void uncertainty_map_t(const at::Tensor& logits, const at::Tensor& out, double T, int64_t mode) {
+  CHECK_F32(logits); CHECK_U8(out);
+  const CalibDims d = calib_dims(logits, at::Tensor(), 1);
+  TORCH_CHECK(T > 0 && std::isfinite(T) && (float)T > 0.f && std::isfinite((float)T),
+              "temperature must be a finite number > 0, got ", T);
+  TORCH_CHECK(mode == 0 || mode == 1, "mode must be 0 (entropy) or 1 (confidence)");
+  TORCH_CHECK(out.numel() == (int64_t)d.N * d.HW, "out must be [N, H, W]");
+  TORCH_CHECK((int64_t)d.N * d.HW <= 2147483647LL * 512, "uncertainty_map: too many pixels in one call");
+  uncertainty_map(f32(logits), out.data_ptr<uint8_t>(), d.N, d.C, d.HW, (float)T, (int)mode, cur_stream());
+}
+
+// ---- boundary metrics (surface.hip)
 
 static void surface_dims_check(int64_t B, int64_t H, int64_t W) {
   TORCH_CHECK(H >= 1 && W >= 1 && H <= kEdtMaxDim && W <= kEdtMaxDim, "distance transform: H and W must be in [1, ",
@@ -1756,6 +1805,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("amp_update", &amp_update_t);
   m.def("ema_update", &ema_update_t);
   m.def("confmat_update", &confmat_update_t);
+  m.def("calib_blocks", [](int64_t pixels) { return (int64_t)calib_blocks((long)pixels); });
+  m.def("calib_stats", &calib_stats_t, py::arg("logits"), py::arg("target"), py::arg("ints"), py::arg("sums"),
+        py::arg("part"), py::arg("T"), py::arg("ignore_index"), py::arg("bins"));
+  m.def("calib_nll_grid", &calib_nll_grid_t);
+  m.def("uncertainty_map", &uncertainty_map_t);
+  m.attr("CALIB_MAX_CLASSES") = kCalibMaxClasses;
+  m.attr("CALIB_MAX_BINS") = kCalibMaxBins;
+  m.attr("CALIB_MAX_K") = kCalibMaxK;
   m.def("surface_labels", &surface_labels_t);
   m.def("surface_boundary", &surface_boundary_t);
   m.def("edt_sq", &edt_sq_t, py::arg("mask"), py::arg("d2"), py::arg("sel") = py::none(), py::arg("half") = 0);

@@ -319,6 +319,22 @@ void bilinear_resize(const float* x, float* y, long NC, int IH, int IW, int OH, 
                      hipStream_t s);
 void colorize(const float* logits, const uint8_t* lut, uint8_t* rgb, int N, int C, long HW, hipStream_t s);
 
+// calibration.hip: reliability statistics, the NLL of a grid of inverse temperatures, uncertainty maps.
+// logits [N][C][HW] fp32, target [N][HW]; a pixel is valid iff t != ignore_index and 0 <= t < C.
+constexpr int kCalibMaxClasses = 64;
+constexpr int kCalibMaxBins = 64;
+constexpr int kCalibMaxK = 64;
+int calib_blocks(long pixels);   // rows of `part`: a function of the pixel count alone
+// ints [2][M] += (bin count, bin hits); sums [M + 2] += (conf_sum[M], nll_sum, brier_sum); part [blocks][M + 2]
+void calib_stats(const float* logits, const int64_t* target, int64_t* ints, double* sums, double* part, int N, int C,
+                 long HW, int ignore_index, int M, float T, hipStream_t s);
+// sums [K] += sum over valid pixels of logsumexp(beta_k z) - beta_k z_t; betas holds kCalibMaxK floats (the first K
+// are read as values, the rest only loaded); part [blocks][K]
+void calib_nll_grid(const float* logits, const int64_t* target, const float* betas, double* sums, double* part, int N,
+                    int C, long HW, int ignore_index, int K, hipStream_t s);
+// out [N][HW] uint8; mode 0: round(255 H(p) / ln C), 1: round(255 (1 - max p) / (1 - 1 / C)); C == 1: logits [0, z]
+void uncertainty_map(const float* logits, uint8_t* out, int N, int C, long HW, float T, int mode, hipStream_t s);
+
 // surface.hip: boundary metrics (HD95 / ASSD / NSD) on an exact integer squared Euclidean distance transform.
 // Images are uint8 [B][H][W] planes; H, W <= kEdtMaxDim.  A map without any set pixel is kEdtNone everywhere.
 constexpr int kEdtMaxDim = 16384;

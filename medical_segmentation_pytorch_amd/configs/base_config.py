@@ -43,6 +43,13 @@ class BaseConfig:
         self.lesion_min_overlap = 0.0  # 'lesion_*' metrics: a component is a hit when at least this fraction of its
                                        # area (and at least one pixel) lies in the other mask
         self.cc_connectivity = 8       # 4 | 8: pixel connectivity of the lesion metrics and the post-processing
+        # calibration (ops/calibration.py; absent from the reference): the 'ece' | 'mce' | 'nll' | 'brier' metrics,
+        # post-hoc temperature scaling and the uncertainty maps of predict mode
+        self.calibration_bins = 15     # 1..64 equal-width confidence bins of the reliability statistics
+        self.calibrate_temperature = False   # fit T on the validation split after training, store it in best.pth
+        self.calibration_rounds = 2    # 1..4 passes over the split, each refining the grid of the one before
+        self.temperature = None        # None: the checkpoint's (1.0 when it has none) | an override > 0
+        self.save_uncertainty = None   # None | 'entropy' | 'confidence': predict mode writes <stem>_unc.png
         self.val_bs = 16
         self.begin_val_epoch = 0
         self.val_interval = 1
@@ -214,6 +221,10 @@ class BaseConfig:
         if self.metrics[0] in ('hd95', 'assd'):
             raise ValueError(f"metrics[0] drives best-checkpoint selection as higher-is-better; '{self.metrics[0]}' is "
                              f"a distance (lower is better) -- put 'dice', 'iou' or 'nsd' first")
+        if self.metrics[0] in ('ece', 'mce', 'nll', 'brier'):
+            raise ValueError(f"metrics[0] drives best-checkpoint selection as higher-is-better; '{self.metrics[0]}' is "
+                             f"a calibration error (lower is better) -- put 'dice', 'iou' or 'nsd' first")
+        self.check_calibration()
         if not 0.0 <= float(self.lesion_min_overlap) <= 1.0:
             raise ValueError(f'lesion_min_overlap must be in [0, 1], got {self.lesion_min_overlap}')
         if self.cc_connectivity not in (4, 8):
@@ -289,6 +300,21 @@ class BaseConfig:
             if 2 * radius >= min(self.crop_h, self.crop_w):
                 raise ValueError(f'aug_blur_sigma {blur!r}: twice the blur radius ({radius}) must be below the crop '
                                  f'({self.crop_h} x {self.crop_w})')
+
+    def check_calibration(self):
+        """Validate the calibration / temperature / uncertainty fields."""
+        for name, lo, hi in (('calibration_bins', 1, 64), ('calibration_rounds', 1, 4)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or not lo <= v <= hi:
+                raise ValueError(f'{name} must be an integer in {lo}..{hi}, got {v!r}')
+            setattr(self, name, int(v))
+        if not isinstance(self.calibrate_temperature, bool):
+            raise ValueError(f'calibrate_temperature must be a bool, got {self.calibrate_temperature!r}')
+        t = self.temperature
+        if t is not None and (isinstance(t, bool) or not isinstance(t, (int, float)) or not 0 < t < float('inf')):
+            raise ValueError(f'temperature must be None or a finite number > 0, got {t!r}')
+        if self.save_uncertainty not in (None, 'entropy', 'confidence'):
+            raise ValueError(f"save_uncertainty must be None, 'entropy' or 'confidence', got {self.save_uncertainty!r}")
 
     INFERENCE_FIELDS = ('infer_window', 'infer_overlap', 'infer_blend', 'infer_sigma_scale', 'infer_batch',
                         'tta_flips', 'tta_average')

@@ -43,6 +43,10 @@ def get_parser():
     _flag(p, 'nsd_tolerance', type=float)
     _flag(p, 'lesion_min_overlap', type=float)
     _flag(p, 'cc_connectivity', type=int, choices=[4, 8])
+    _flag(p, 'calibration_bins', type=int)
+    _flag(p, 'calibrate_temperature', action='store_true')
+    _flag(p, 'calibration_rounds', type=int)
+    _flag(p, 'temperature', type=float)
     _flag(p, 'val_bs', type=int)
     _flag(p, 'begin_val_epoch', type=int)
     _flag(p, 'val_interval', type=int)
@@ -64,6 +68,7 @@ def get_parser():
     _flag(p, 'save_mask', action='store_false')
     _flag(p, 'blend_prediction', action='store_false')
     _flag(p, 'blend_alpha', type=float)
+    _flag(p, 'save_uncertainty', type=str, choices=['entropy', 'confidence'])
     _flag(p, 'post_fill_holes', action='store_true')
     _flag(p, 'post_min_area', type=int)
     _flag(p, 'post_keep_largest', action='store_true')

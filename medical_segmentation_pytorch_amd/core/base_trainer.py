@@ -78,6 +78,7 @@ class BaseTrainer:
             self.logger.info(f'engine: {"fused MI355X HIP kernels" if self.fused else "eager PyTorch"} '
                              f'on {self.device}')
         self.optimizer = None
+        self.temperature = 1.0     # softmax temperature of the probabilities (calibration metrics, uncertainty maps)
         if config.is_testing:
             assert config.load_ckpt, 'Need to load a pretrained checkpoint in `test` mode.'
             self.test_loader = get_test_loader(config)
@@ -146,6 +147,9 @@ class BaseTrainer:
         best_score = self.best_score
         if config.save_ckpt:
             best_score = self.val_best(config, self.val_loader)
+            if getattr(config, 'calibrate_temperature', False):
+                # fitted on the validation split: the test-split numbers below are then held-out calibrated ones
+                self.calibrate(config, self.val_loader)
             if config.use_test_set:
                 self.test_score = self.val_best(config, self.test_loader)
         if self.watchdog is not None:
@@ -183,11 +187,20 @@ class BaseTrainer:
     def predict(self, config):
         raise NotImplementedError()
 
+    def calibrate(self, config, loader, ckpt_path=None):
+        raise NotImplementedError()
+
+    def checkpoint_temperature(self, config, ckpt):
+        """``config.temperature`` when set (an override), else the checkpoint's, else 1.0 (an older checkpoint)."""
+        override = getattr(config, 'temperature', None)
+        return float(override) if override is not None else float(ckpt.get('temperature', 1.0))
+
     # ------------------------------------------------------------------------------------------------
     def load_ckpt(self, config):
         if config.load_ckpt and config.load_ckpt_path and os.path.isfile(config.load_ckpt_path):
             ckpt = torch.load(config.load_ckpt_path, map_location=self.device, weights_only=True)
             de_parallel(self.model).load_state_dict(ckpt['state_dict'])
+            self.temperature = self.checkpoint_temperature(config, ckpt)
             if self.main_rank and self.logger:
                 self.logger.info(f'Load model state dict from {config.load_ckpt_path}')
             if not config.is_testing and config.resume_training and ckpt.get('optimizer') is not None:
@@ -262,6 +275,7 @@ class BaseTrainer:
         model = de_parallel(self.model)
         ckpt = torch.load(ckpt_path, map_location=self.device, weights_only=True)
         model.load_state_dict(ckpt['state_dict'])
+        self.temperature = self.checkpoint_temperature(config, ckpt)
         del ckpt
         self.ema_model.ema = deepcopy(model).eval()
         val_score = self.validate(config, loader, val_best=True)

@@ -24,9 +24,11 @@ from PIL import Image
 
 from ..models import get_teacher_model
 from ..ops.bn import flush_pending
+from ..ops.calibration import uncertainty_map
 from ..ops.components import postprocess
 from ..runtime.trainer_engine import StepEngine, iteration
 from ..utils import FusedModel, de_parallel, get_colormap, get_seg_metrics, sampler_set_epoch
+from ..utils.metrics import _CalibrationMetric
 from .base_trainer import BaseTrainer
 from ..ops.resample import colorize, resize_bilinear
 from ..ops.tiled import sliding_window_inference
@@ -50,6 +52,19 @@ def _finite_or_none(v):
     if isinstance(v, list):
         return [_finite_or_none(x) for x in v]
     return v if v == v and abs(v) != float('inf') else None
+
+
+def add_checkpoint_temperature(path, T):
+    """Add (or replace) the float ``temperature`` key of the checkpoint at ``path`` in place; every other key is
+    written back as it was read."""
+    T = float(T)
+    if not 0 < T < float('inf'):
+        raise ValueError(f'temperature must be a finite number > 0, got {T!r}')
+    ckpt = torch.load(path, map_location='cpu', weights_only=True)
+    ckpt['temperature'] = T
+    tmp = f'{path}.tmp'
+    torch.save(ckpt, tmp)
+    os.replace(tmp, path)
 
 
 class SegTrainer(BaseTrainer):
@@ -225,13 +240,10 @@ class SegTrainer(BaseTrainer):
             self._inference_logged = True
             self.logger.info(f'Sliding-window inference / flip TTA: {tiled} (window None: the whole image)\n')
 
-    @torch.no_grad()
-    def validate(self, config, loader, val_best=False):
-        self.config_ref = config
-        t_val = time.perf_counter()
+    def _eval_batches(self, config, loader, tiled):
+        """The evaluation forward of ``validate`` and ``calibrate`` over ``loader``: yields (logits at the masks'
+        resolution -- two-class for a sigmoid head --, masks)."""
         pbar = _tqdm(loader, self.main_rank and config.progress_bar)
-        tiled = config.inference_settings()
-        self._log_inference(tiled)
         for images, masks in pbar:
             images = images.to(self.device, dtype=torch.float32)
             _, _, H, W = images.shape
@@ -251,6 +263,18 @@ class SegTrainer(BaseTrainer):
                 preds = resize_bilinear(preds, masks.size()[1:], align_corners=True)
             if preds.shape[1] == 1:   # binary (sigmoid) path -> two-class logits for the confmat
                 preds = torch.cat([torch.zeros_like(preds), preds], 1)
+            yield preds, masks
+
+    @torch.no_grad()
+    def validate(self, config, loader, val_best=False):
+        self.config_ref = config
+        t_val = time.perf_counter()
+        tiled = config.inference_settings()
+        self._log_inference(tiled)
+        calib = [m for m in self.metrics if isinstance(m, _CalibrationMetric)]
+        if calib:
+            calib[0].acc.set_temperature(self.temperature)
+        for preds, masks in self._eval_batches(config, loader, tiled):
             for metric in self.metrics:
                 metric.update(preds.detach().float(), masks)
         scores = [metric.compute() for metric in self.metrics]
@@ -286,10 +310,41 @@ class SegTrainer(BaseTrainer):
             rec['inference'] = {k: (list(v) if isinstance(v, tuple) else v) for k, v in tiled.items()}
         for m, v in self.last_scores.items():
             rec[m] = _finite_or_none(v.tolist())
+        if calib:     # the reliability diagram behind the calibration metrics (all ranks)
+            rel = calib[0].reliability()
+            rec['calibration'] = {'temperature': float(self.temperature), 'bins': int(calib[0].acc.bins),
+                                  'count': rel['count'].tolist(),
+                                  'accuracy': _finite_or_none(rel['accuracy'].tolist()),
+                                  'confidence': _finite_or_none(rel['confidence'].tolist())}
         self.val_history.append(rec)
         for metric in self.metrics:
             metric.reset()
         return score
+
+    @torch.no_grad()
+    def calibrate(self, config, loader, ckpt_path=None):
+        """Post-hoc temperature scaling of the model ``validate`` evaluates (after ``val_best``: the best checkpoint):
+        fit T on ``loader`` through the evaluation forward (resize, sliding windows, TTA), keep it in
+        ``self.temperature``, add it to ``best.pth`` (or ``ckpt_path``) and validate once more at the new temperature.
+        The argmax does not depend on T, so the label-map metrics are those of the validation before."""
+        from ..ops.calibration import fit_temperature
+        self.config_ref = config
+        tiled = config.inference_settings()
+        T, info = fit_temperature(
+            lambda: ((p.detach().float(), m) for p, m in self._eval_batches(config, loader, tiled)),
+            config.ignore_index, config.calibration_rounds, group=getattr(config, 'dist_group', None),
+            device=self.device, return_info=True)
+        self.temperature = T
+        if self.main_rank:
+            if self.logger:
+                self.logger.info(f'\nTemperature scaling: T = {T:.5f} after {info["rounds"]} rounds\n')
+            add_checkpoint_temperature(f'{config.save_dir}/best.pth' if ckpt_path is None else ckpt_path, T)
+        if config.DDP:      # rank 0 alone rewrote the checkpoint that the next val_best reads
+            from ..utils.parallel import get_group
+            torch.distributed.barrier(group=get_group(config))
+        self.validate(config, loader, val_best=True)
+        self.val_history[-1]['calibrated'] = True
+        return T
 
     @torch.no_grad()
     def predict(self, config):
@@ -308,6 +363,9 @@ class SegTrainer(BaseTrainer):
                              f'connectivity {getattr(config, "cc_connectivity", 8)}\n')
         tiled = config.inference_settings()
         self._log_inference(tiled)
+        unc_mode = getattr(config, 'save_uncertainty', None)
+        if unc_mode and self.logger:
+            self.logger.info(f'Saving {unc_mode} uncertainty maps at temperature {self.temperature:.5f}\n')
         for images, images_aug, img_names in _tqdm(self.test_loader, config.progress_bar):
             images_aug = images_aug.to(self.device, dtype=torch.float32)
             if tiled is None:
@@ -315,6 +373,8 @@ class SegTrainer(BaseTrainer):
             else:
                 preds = sliding_window_inference(images_aug, lambda x: fwd(x).float(),
                                                  **{**tiled, 'window': tiled['window'] or images_aug.shape[2:]})
+            # (from the final logits, blended or not, before any clean-up of the label map)
+            unc = uncertainty_map(preds.float(), self.temperature, unc_mode).cpu().numpy() if unc_mode else None
             if clean:
                 # the label map stays on the device: argmax (logit > 0 for a sigmoid head), clean-up, colours
                 labels = (preds[:, 0] > 0) if preds.shape[1] == 1 else preds.argmax(1)
@@ -333,6 +393,8 @@ class SegTrainer(BaseTrainer):
                 pred = Image.fromarray(preds[i].astype(np.uint8))
                 if config.save_mask:
                     pred.save(save_path)
+                if unc is not None:
+                    Image.fromarray(unc[i]).save(os.path.splitext(save_path)[0] + '_unc.png')
                 if config.blend_prediction:
                     blend_path = save_path.replace(f'.{suffix}', f'_blend.{suffix}')
                     image = Image.fromarray(images[i].astype(np.uint8))

@@ -19,6 +19,11 @@ Lesion-wise metrics (an addition too): ``LesionRecall``, ``LesionPrecision`` and
 components instead of pixels -- how many ground-truth lesions were found and how many predicted blobs were false
 alarms (``ops/components.py`` has the semantics; on MI355X the ``components.hip`` labelling kernels).  They share
 one :class:`LesionAccumulator` in the same way.
+
+Calibration metrics (an addition as well): ``ExpectedCalibrationError``, ``MaximumCalibrationError``,
+``NegativeLogLikelihood`` and ``BrierScore`` score the probabilities instead of the label map, at the temperature of
+their shared :class:`CalibrationAccumulator` (``ops/calibration.py`` has the semantics; on MI355X the
+``calibration.hip`` kernels).
 """
 from __future__ import annotations
 
@@ -346,11 +351,121 @@ class LesionF1(_LesionMetric):
         return f1, (c[0] > 0) | (c[2] > 0)
 
 
+class CalibrationAccumulator(nn.Module):
+    """State of the calibration metrics: int64 ``ints [2, M]`` (per-bin pixel count and hits) and fp64
+    ``sums [M + 2]`` (per-bin confidence sum, NLL sum, Brier sum), plus the one-element ``temperature`` the
+    probabilities are taken at.  Shared by the metric objects built from one config exactly as
+    :class:`SurfaceAccumulator` is: a batch is scored once however many of the four see it, and ``reset`` by any
+    of them zeroes it once (the temperature stays)."""
+
+    def __init__(self, num_classes, ignore_index=None, bins=15):
+        super().__init__()
+        from ..ops.calibration import new_state
+        self.num_classes = num_classes
+        self.ignore_index = ignore_index
+        st = new_state(bins)
+        self.bins = st['ints'].shape[1]
+        self.register_buffer('ints', st['ints'])
+        self.register_buffer('sums', st['sums'])
+        self.register_buffer('temperature', torch.ones(1, dtype=torch.float64))
+        self._t = 1.0      # host copy of ``temperature``: the kernels take it by value, without a device read
+        self._last, self._seen = None, set()
+
+    def set_temperature(self, T):
+        from ..ops.calibration import _check_temperature
+        self._t = _check_temperature(T)
+        self.temperature.fill_(self._t)
+
+    @torch.no_grad()
+    def update(self, preds, target, owner=None):
+        key = tuple((t.data_ptr(), tuple(t.shape), t.stride(), t.dtype, t._version) for t in (preds, target))
+        if self._last is not None and self._last[0] == key and owner is not None and owner not in self._seen:
+            self._seen.add(owner)
+            return
+        from ..ops.calibration import calibration_stats, state_views
+        dev = self.sums.device
+        calibration_stats(preds.to(dev), target.to(dev), state_views(self.ints, self.sums), self._t,
+                          self.ignore_index, self.bins)
+        self._last, self._seen = (key, preds, target), {owner}
+
+    def reset(self):
+        self.ints.zero_()
+        self.sums.zero_()
+        self._last, self._seen = None, set()
+
+
+class _CalibrationMetric(nn.Module):
+    """One of (ece, mce, nll, brier) of the shared state (``ops/calibration.py`` has the semantics); nan when no
+    pixel was scored; lower is better.  ``compute`` all-reduces the packed state once (SUM over ``group``)."""
+    index = 0
+
+    def __init__(self, num_classes=2, ignore_index=None, bins=15, sync=True, group=None, accumulator=None):
+        super().__init__()
+        if num_classes < 2:
+            raise ValueError('calibration metrics need num_classes >= 2')
+        self.group = group
+        self.num_classes = num_classes
+        self.sync = sync
+        self.acc = accumulator if accumulator is not None else CalibrationAccumulator(num_classes, ignore_index, bins)
+        if self.acc.num_classes != num_classes:
+            raise ValueError('shared accumulator was built for another number of classes')
+
+    def update(self, preds, target):
+        self.acc.update(preds, target, owner=id(self))
+
+    def reset(self):
+        self.acc.reset()
+
+    def _synced(self):
+        """(counts ``[2, M]`` fp64, sums ``[M + 2]``) over all ranks; the counts are exact below 2^53"""
+        a = self.acc
+        st = torch.cat([a.ints.reshape(-1).double(), a.sums])
+        if self.sync and dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            dist.all_reduce(st, group=self.group)
+        return st[:2 * a.bins].view(2, a.bins), st[2 * a.bins:]
+
+    def reliability(self):
+        """Per bin over all ranks (a collective like ``compute``): int64 ``count``, and fp64 ``accuracy`` and mean
+        ``confidence`` (nan in an empty bin)."""
+        ints, sums = self._synced()
+        den = ints[0].clamp_min(1.0)
+        nan = torch.full_like(den, float('nan'))
+        return {'count': ints[0].round().long(), 'accuracy': torch.where(ints[0] > 0, ints[1] / den, nan),
+                'confidence': torch.where(ints[0] > 0, sums[:self.acc.bins] / den, nan)}
+
+    def compute(self):
+        from ..ops.calibration import metrics_from_state
+        return metrics_from_state(*self._synced())[self.index].float()
+
+
+class ExpectedCalibrationError(_CalibrationMetric):
+    """``sum_b |correct_b - conf_sum_b| / V``: the mean gap between confidence and accuracy."""
+    index = 0
+
+
+class MaximumCalibrationError(_CalibrationMetric):
+    """The largest per-bin gap between accuracy and mean confidence over the non-empty bins."""
+    index = 1
+
+
+class NegativeLogLikelihood(_CalibrationMetric):
+    """Mean of ``logsumexp(z / T) - z_label / T`` over the valid pixels."""
+    index = 2
+
+
+class BrierScore(_CalibrationMetric):
+    """Mean of ``sum_c (p_c - y_c)^2`` over the valid pixels."""
+    index = 3
+
+
 SURFACE_METRICS = {'hd95': HausdorffDistance95, 'assd': AverageSurfaceDistance, 'nsd': SurfaceDice}
 LESION_METRICS = {'lesion_recall': LesionRecall, 'lesion_precision': LesionPrecision, 'lesion_f1': LesionF1}
-LOWER_IS_BETTER = ('hd95', 'assd')
+CALIBRATION_METRICS = {'ece': ExpectedCalibrationError, 'mce': MaximumCalibrationError,
+                       'nll': NegativeLogLikelihood, 'brier': BrierScore}
+LOWER_IS_BETTER = ('hd95', 'assd', 'ece', 'mce', 'nll', 'brier')
 _SURFACE_ACC = weakref.WeakKeyDictionary()     # config object -> the accumulator its surface metrics share
 _LESION_ACC = weakref.WeakKeyDictionary()      # config object -> the accumulator its lesion metrics share
+_CALIBRATION_ACC = weakref.WeakKeyDictionary()     # config object -> the accumulator its calibration metrics share
 
 
 def _lesion_metric(config, metric_name, nc, group):
@@ -368,9 +483,24 @@ def _lesion_metric(config, metric_name, nc, group):
     return LESION_METRICS[metric_name](num_classes=nc, group=group, accumulator=acc)
 
 
+def _calibration_metric(config, metric_name, nc, group):
+    try:
+        acc, store = _CALIBRATION_ACC.get(config), _CALIBRATION_ACC.__setitem__
+    except TypeError:      # a config object that cannot be weakly referenced keeps it itself
+        acc, store = getattr(config, '_calibration_accumulator', None), \
+            lambda c, a: setattr(c, '_calibration_accumulator', a)
+    bins = int(getattr(config, 'calibration_bins', 15))
+    if acc is None or acc.num_classes != nc or acc.ignore_index != config.ignore_index or acc.bins != bins:
+        acc = CalibrationAccumulator(nc, config.ignore_index, bins)
+        store(config, acc)
+    return CALIBRATION_METRICS[metric_name](num_classes=nc, group=group, accumulator=acc)
+
+
 def get_seg_metrics(config, metric_name):
     nc = max(config.num_class, 2)          # num_class == 1 (sigmoid) is scored as background/foreground
     group = getattr(config, 'dist_group', None)
+    if metric_name in CALIBRATION_METRICS:
+        return _calibration_metric(config, metric_name, nc, group)
     if metric_name in LESION_METRICS:
         return _lesion_metric(config, metric_name, nc, group)
     if metric_name in SURFACE_METRICS:
