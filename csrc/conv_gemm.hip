@@ -25,6 +25,16 @@
 // Epilogue: bias / accumulate / bf16 round, 8-B NHWC stores into the row's output group, and the
 // per-channel BatchNorm partials (sum, sum^2 of the stored values -- or, for the data-gradient of a
 // BN output, the BN-backward partials) reduced across lanes and waves in LDS, one row per pixel tile.
+// Stores count in vmcnt and a load's wait also waits for every store issued before it, so no epilogue load
+// sits behind a store: the coefficient rows (BN scale / shift / mean, bias) are read once per block into the
+// staging LDS, and a fragment row issues all its bn_y / old-output loads, unconditionally at clamped
+// addresses, before its first store.  Until round 8 every group of 4 output rows loaded bn_y and three
+// coefficient vectors behind the previous group's store and waited vmcnt(0): 16-24 dependent store + load round
+// trips per wave.  The row sums leave the DPP rows through LDS (lanes 0 / 16 / 32 / 48 write, the final pass
+// adds the pair in the old order), not through ~150 ds_bpermute + waited writes per wave.  Bitwise the same
+// results; in-kernel stamps at batch 320, drain per block: BN-backward 20-33 -> 6-13 us, accumulate 10-17 ->
+// 4.5-11 us, forward statistics 7-14.5 -> 6.5-11 us, plain data-gradient 3.4-7.5 -> 2.7-6 us
+// (profiles/r08/gemm_epilogue/README.md).
 #include <algorithm>
 
 #include "common.h"
@@ -130,11 +140,11 @@ struct GemmCfg {
   static constexpr int ROWB = BK * 2, SLOTS = BK / 8, RPI = 1024 / ROWB;
   static constexpr int A_BYTES = TCO * ROWB, B_BYTES = TPX * ROWB, STAGE = A_BYTES + B_BYTES;
   static constexpr int A_INS = TCO / RPI / NW, B_INS = TPX / RPI / NW;   // DMA instructions per wave per stage
-  // (the epilogue's stats scratch reuses the stages)
+  // (the epilogue's stats scratch and coefficient rows reuse the stages)
   static constexpr int LDS = NS * STAGE;
   static_assert(BK == 64 || BK == 32, "stage width");
   static_assert(TCO % (RPI * NW) == 0 && TPX % (RPI * NW) == 0, "tile rows must split evenly over the waves");
-  static_assert(2 * WN * TCO * 4 <= NS * STAGE, "stats scratch must fit in the staging LDS");
+  static_assert((4 * WN + 3) * TCO * 4 <= NS * STAGE, "stats scratch + coefficient rows must fit in the staging LDS");
   static_assert(NS >= 2 && NS <= 5 && (NS - 2) * (A_INS + B_INS) < 64, "pipeline depth / vmcnt range");
   static_assert(NW % 2 == 0, "one logical k slot per lane across the wave's DMA instructions");
   // XOR swizzle of the 16-B slots of a row (source side of the DMA, undone by the fragment reads): the 16
@@ -366,98 +376,179 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_gemm_kernel(ConvArgs a
         for (int j = 0; j < FN; ++j) acc[i][j] = mfma32(af[i], bfr[j], acc[i][j]);
     }
   }
+  // ---- the epilogue's per-channel coefficient rows (BN-backward: scale, shift, mean; else the bias), one tile
+  // row per thread, read once per block and parked in the staging LDS once every wave is done with the stages.
+  // (Until round 8 every group of 4 output rows re-read them from global memory behind the previous group's
+  // store.  Read before the K walk they would hide their round trip, but the three registers they then hold
+  // through the main loop spill in the four-blocks-per-CU tile.)
+  static_assert(C::TCO <= C::NT, "one coefficient row element per thread");
+  const bool has_bias = !BNE && a.bias != nullptr;
+  float cpre[BNE ? 3 : 1] = {};
+  {
+    const int co = co0 + tid;
+    const bool in = tid < C::TCO && co < rows;
+    if constexpr (BNE) {   // (Go == 1: the row index is the channel)
+#pragma unroll
+      for (int u = 0; u < 3; ++u) cpre[u] = in ? a.bn_coef[(long)u * g.Cgo + co] : 0.f;
+    } else if (has_bias) {
+      const int cl = in ? co - (co / g.Cgo) * g.Cgo : 0;
+      cpre[0] = (in && cl < g.Cgo_l) ? a.bias[cl] : 0.f;
+    }
+  }
   __syncthreads();   // every wave is done with the stages before the epilogue reuses them
 #ifdef GK_STAMP
   const unsigned long long ts2 = gk_clock();
 #endif
 
   // ---- epilogue.  32x32 D layout: lane holds column (pixel) lr, rows 8q + 4h + r in register 4q + r.
-  float* s_st = reinterpret_cast<float*>(smem);   // [WN][2][TCO] per-pixel-wave-column channel partials
-  const bool stats = a.stat_part != nullptr;
+  // No load sits behind a store it does not depend on (vmcnt counts stores too, and a load's wait also waits
+  // for every store issued before it): the coefficient rows come from LDS (cpre, above), and a fragment row
+  // issues ALL its bn_y / old-output loads -- unconditionally, at clamped addresses, since a load under a
+  // per-element condition compiles to a branch and its own vmcnt(0) -- before its first store.
+  float* s_st = reinterpret_cast<float*>(smem);   // [WN][sum | sq][16-lane half][TCO] channel partials per pixel wave
+  float* s_co = s_st + 4 * WN * C::TCO;           // [3][TCO] coefficient rows of the tile's channels
+  // (BNE launches always carry stat_part; saying so keeps the compiler from sinking the partials' math of a whole
+  // fragment row behind its stores, into the `if (stats)` below, with every group's coefficients live at once)
+  const bool stats = BNE || a.stat_part != nullptr;
+  if (BNE || has_bias) {
+    if (tid < C::TCO) {
+#pragma unroll
+      for (int u = 0; u < (BNE ? 3 : 1); ++u) s_co[u * C::TCO + tid] = cpre[u];
+    }
+    __syncthreads();
+  }
 #pragma unroll
   for (int i = 0; i < FM; ++i) {
     const int rb = wm * FM * 32 + i * 32;   // tile-local row base of this fragment row
-    uint16_t* yb[4];
+    uint16_t* yb[4];   // the 4-row group's output pointer (rows past the layer: group 0's, never stored through)
     int cl4[4];
-    float cs[16], cq[16];
+    bool cok[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int cb = co0 + rb + 8 * q + 4 * lh;
-      const int og = cb < rows ? cb / g.Cgo : 0;
-      cl4[q] = cb - og * g.Cgo;
+      cok[q] = cb < rows;
+      const int og = (!BNE && cok[q]) ? cb / g.Cgo : 0;
+      cl4[q] = cok[q] ? cb - og * g.Cgo : 0;
       uint16_t* yg = a.y[0];
+      if constexpr (!BNE) {   // (BNE: Go == 1)
 #pragma unroll
-      for (int t = 1; t < kMaxGroups; ++t) yg = og == t ? a.y[t] : yg;
-      yb[q] = cb < rows ? yg + cl4[q] : nullptr;
+        for (int t = 1; t < kMaxGroups; ++t) yg = og == t ? a.y[t] : yg;
+      }
+      yb[q] = yg + cl4[q];
     }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { cs[e] = 0.f; cq[e] = 0.f; }
+    // The lane's pixels (pixels past the tail: a pixel of the tile, never stored).  BNE (one output group, no
+    // phase map): a 32-bit byte offset from the tile's first pixel, so that every load and store of the row is
+    // uniform base + one address register; else the 64-bit element offset in an output group.
+    long mo[FN];
+    uint32_t po[FN];
+    bool mok[FN];
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
-      long m = px0 + wn * FN * 32 + j * 32 + lr;
-      if (m >= gg.M) continue;
-      if (gg.ps) {   // phase launch: the phase-grid pixel's place in the full output
+      const int ml = wn * FN * 32 + j * 32 + lr;
+      mok[j] = px0 + ml < gg.M;
+      po[j] = mok[j] ? (uint32_t)ml * (uint32_t)g.Cgo * 2u : 0u;
+      long m = mok[j] ? px0 + ml : px0;
+      if (!BNE && gg.ps) {   // phase launch (never with BNE): the phase-grid pixel's place in the full output
         const long n = m / gg.OHWp, r = m - n * gg.OHWp;
         const long oh = r / gg.OWp, ow = r - oh * gg.OWp;
         m = n * gg.OHWf + (gg.py + gg.ps * oh) * gg.OW + gg.px + gg.ps * ow;
       }
+      mo[j] = m * g.Cgo;
+    }
+    const uint8_t* bn_t = reinterpret_cast<const uint8_t*>(BNE ? a.bn_y + px0 * g.Cgo : nullptr);   // (uniform)
+    uint8_t* y_t = reinterpret_cast<uint8_t*>(a.y[0] + px0 * g.Cgo);
+    auto yaddr = [&](int j, int q) -> uint16_t* {
+      if constexpr (BNE) return reinterpret_cast<uint16_t*>(y_t + (po[j] + 2u * (uint32_t)cl4[q]));
+      else return yb[q] + mo[j];
+    };
+    uint2 pre[FN][4];   // BN-backward: bn_y at the output's place; accumulate: the old output
+    if constexpr (BNE) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (yb[q] == nullptr) continue;
-        uint16_t* yp = yb[q] + m * g.Cgo;
+      for (int j = 0; j < FN; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pre[j][q] = *reinterpret_cast<const uint2*>(bn_t + (po[j] + 2u * (uint32_t)cl4[q]));
+    } else if (a.accum) {
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) pre[j][q] = *reinterpret_cast<const uint2*>(yaddr(j, q));
+    }
+    __builtin_amdgcn_sched_barrier(0);   // (the loads' addresses die here: nothing of the row's math moves above)
+    float cs[16], cq[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) { cs[e] = 0.f; cq[e] = 0.f; }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int lrow = rb + 8 * q + 4 * lh;   // tile-local row of register 4q
+      float c0[4] = {0.f, 0.f, 0.f, 0.f}, c1[4] = {0.f, 0.f, 0.f, 0.f}, c2[4] = {0.f, 0.f, 0.f, 0.f};
+      if (BNE || has_bias) {
+        const float4 t0 = *reinterpret_cast<const float4*>(s_co + lrow);
+        c0[0] = t0.x; c0[1] = t0.y; c0[2] = t0.z; c0[3] = t0.w;
+      }
+      if constexpr (BNE) {
+        const float4 t1 = *reinterpret_cast<const float4*>(s_co + C::TCO + lrow);
+        const float4 t2 = *reinterpret_cast<const float4*>(s_co + 2 * C::TCO + lrow);
+        c1[0] = t1.x; c1[1] = t1.y; c1[2] = t1.z; c1[3] = t1.w;
+        c2[0] = t2.x; c2[1] = t2.y; c2[2] = t2.z; c2[3] = t2.w;
+      }
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        const bool ok = cok[q] && mok[j];
         float v[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = acc[i][j][4 * q + r];
-        if (a.bias != nullptr) {
+        if (has_bias) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = cl4[q] + r < g.Cgo_l ? v[r] + a.bias[cl4[q] + r] : 0.f;
+          for (int r = 0; r < 4; ++r) v[r] = cl4[q] + r < g.Cgo_l ? v[r] + c0[r] : 0.f;
         }
         if (!BNE && a.accum) {   // y += conv(x): sibling launches' data-gradients into one tensor
-          const uint2 ov = *reinterpret_cast<const uint2*>(yp);
+          const uint2 ov = pre[j][q];
           v[0] += __uint_as_float(ov.x << 16); v[1] += __uint_as_float(ov.x & 0xffff0000u);
           v[2] += __uint_as_float(ov.y << 16); v[3] += __uint_as_float(ov.y & 0xffff0000u);
         }
         const uint32_t lo = pack2(v[0], v[1]), hi = pack2(v[2], v[3]);
-        st_stream8(yp, lo, hi);
+        if (ok) st_stream8(yaddr(j, q), lo, hi);
         // statistics of the STORED (bf16-rounded) values, as a BN reading this tensor sees them
         const float w4[4] = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u),
                              __uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u)};
         if constexpr (BNE) {   // BN-backward partials of the BN whose output this data-gradient is (Go == 1)
-          const int cb = cl4[q];
-          const uint2 yy = *reinterpret_cast<const uint2*>(a.bn_y + m * g.Cgo + cb);
-          const float4 sc = *reinterpret_cast<const float4*>(a.bn_coef + cb);
-          const float4 sh = *reinterpret_cast<const float4*>(a.bn_coef + g.Cgo + cb);
-          const float4 mu = *reinterpret_cast<const float4*>(a.bn_coef + 2 * g.Cgo + cb);
+          const uint2 yy = pre[j][q];
           const float y4[4] = {__uint_as_float(yy.x << 16), __uint_as_float(yy.x & 0xffff0000u),
                                __uint_as_float(yy.y << 16), __uint_as_float(yy.y & 0xffff0000u)};
-          const float s4[4] = {sc.x, sc.y, sc.z, sc.w}, h4[4] = {sh.x, sh.y, sh.z, sh.w};
-          const float m4[4] = {mu.x, mu.y, mu.z, mu.w};
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float gr = (!a.bn_relu || fmaf(y4[r], s4[r], h4[r]) > 0.f) ? w4[r] : 0.f;
-            cs[4 * q + r] += gr;
-            cq[4 * q + r] = fmaf(gr, y4[r] - m4[r], cq[4 * q + r]);
+          for (int r = 0; r < 4; ++r) {   // c0 = scale, c1 = shift, c2 = mean
+            const float gr = (!a.bn_relu || fmaf(y4[r], c0[r], c1[r]) > 0.f) ? w4[r] : 0.f;
+            cs[4 * q + r] = ok ? cs[4 * q + r] + gr : cs[4 * q + r];
+            cq[4 * q + r] = ok ? fmaf(gr, y4[r] - c2[r], cq[4 * q + r]) : cq[4 * q + r];
           }
         } else {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            cs[4 * q + r] += w4[r];
-            cq[4 * q + r] = fmaf(w4[r], w4[r], cq[4 * q + r]);
+            cs[4 * q + r] = ok ? cs[4 * q + r] + w4[r] : cs[4 * q + r];
+            cq[4 * q + r] = ok ? fmaf(w4[r], w4[r], cq[4 * q + r]) : cq[4 * q + r];
           }
         }
       }
+      if constexpr (BNE && OCC >= 4) {
+        // The 128-register tile: pin this group's partials HERE.  Left alone the compiler issues the row's stores
+        // first and the partials' math behind them, every group's coefficients (48 registers) live at once: spills.
+#pragma unroll
+        for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(cs[4 * q + r]), "+v"(cq[4 * q + r])::"memory");
+      }
     }
     if (stats) {
-      // sum over the 32 pixel lanes of each half: DPP row sums (16 lanes) + one swap of the row pair
+      // sum over the 16 pixel lanes of each DPP row: lanes 0 / 16 (rows 8q + r) and 32 / 48 (rows 8q + 4 + r)
+      // park their row sums; the final pass adds the pair (lanes 0-15) + (lanes 16-31), what the bpermute swap
+      // of rounds 3-7 added here -- 32 independent DPP chains and 32 unwaited LDS writes, no shuffle, no wait
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float s = row16_sum(cs[e]), q = row16_sum(cq[e]);
-        s += __shfl_xor(s, 16, 64);
-        q += __shfl_xor(q, 16, 64);
-        if (lr == 0) {
-          const int row = rb + 8 * (e >> 2) + 4 * lh + (e & 3);
-          s_st[(wn * 2 + 0) * C::TCO + row] = s;
-          s_st[(wn * 2 + 1) * C::TCO + row] = q;
+      for (int e = 0; e < 16; ++e) { cs[e] = row16_sum(cs[e]); cq[e] = row16_sum(cq[e]); }
+      if ((lane & 15) == 0) {
+        float* ps = s_st + ((wn * 2 + 0) * 2 + ((lane >> 4) & 1)) * C::TCO + rb + 4 * lh;
+        float* pq = s_st + ((wn * 2 + 1) * 2 + ((lane >> 4) & 1)) * C::TCO + rb + 4 * lh;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          ps[8 * (e >> 2) + (e & 3)] = cs[e];
+          pq[8 * (e >> 2) + (e & 3)] = cq[e];
         }
       }
     }
@@ -478,8 +569,8 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_gemm_kernel(ConvArgs a
 #pragma unroll
       for (int w = 0; w < WPH; ++w) {
         const int wv = hb * WPH + w;
-        s += s_st[(wv * 2 + 0) * C::TCO + c];
-        q += s_st[(wv * 2 + 1) * C::TCO + c];
+        s += s_st[((wv * 2 + 0) * 2 + 0) * C::TCO + c] + s_st[((wv * 2 + 0) * 2 + 1) * C::TCO + c];
+        q += s_st[((wv * 2 + 1) * 2 + 0) * C::TCO + c] + s_st[((wv * 2 + 1) * 2 + 1) * C::TCO + c];
       }
       a.stat_part[(srow * 2 + 0) * rows + co] = s;
       a.stat_part[(srow * 2 + 1) * rows + co] = q;

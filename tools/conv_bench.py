@@ -84,7 +84,8 @@ def main():
     ap.add_argument('--gemm-cfg', type=int, default=-1, help='force one LDS-DMA GEMM tile configuration (A/B)')
     ap.add_argument('--gemm-stamps', action='store_true',
                     help='in-kernel clock stamps per block (needs a -DGK_STAMP side build loaded through MSP_C_SO): '
-                    'median fill / main loop / drain per layer, forward and data-gradient')
+                    'median fill / main loop / drain per layer: forward, data-gradient, and the data-gradient '
+                    'through the accumulate and the BN-backward epilogues')
     ap.add_argument('--only', default='', help='substring filter on layer names')
     ap.add_argument('--levels', default='', help='comma list of levels to run (e.g. 3,4,5,6)')
     ap.add_argument('--prologue', action='store_true',
@@ -134,11 +135,29 @@ def main():
         dxs = [torch.empty_like(x)]
         dims_d = [n, oh, ow, plan.Go, plan.Cgo, hw, hw, 1, plan.Cgi, ci, plan.T, Kp_d, s]
         bdy, bdx = [t[0] for t in plan.taps_bwd], [t[1] for t in plan.taps_bwd]
-        t_d = timeit(lambda: C.conv_fwd(gys, wd, dxs, None, None, dims_d, bdy, bdx, s > 1), a.iters)
+        f_d = lambda: C.conv_fwd(gys, wd, dxs, None, None, dims_d, bdy, bdx, s > 1)   # noqa: E731
+        t_d = timeit(f_d, a.iters)
+        # the same data-gradient through the two other GEMM epilogues: accumulating into dL/dx, and (stride 1)
+        # with the BN-backward partials of a BN(+ReLU) whose output this conv read (random y, coefficients as in
+        # tests/test_gpu_conv_gemm.py)
+        f_a = lambda: C.conv_fwd(gys, wd, dxs, None, None, dims_d, bdy, bdx, s > 1, accumulate=True)   # noqa: E731
+        dxs[0].zero_()
+        t_a = timeit(f_a, a.iters)
+        f_b, t_b = None, None
+        if s == 1:
+            bn_y = torch.randn(n, hw, hw, plan.Cgi, device=dev).to(torch.bfloat16)
+            coef = torch.zeros(3, plan.Cgi, device=dev)
+            coef[0, :ci] = torch.rand(ci, device=dev) + 0.5
+            coef[1, :ci] = torch.randn(ci, device=dev) * 0.2
+            coef[2, :ci] = torch.randn(ci, device=dev) * 0.1
+            part_d = torch.empty(C.conv_stat_blocks(dims_d, bdy, bdx, False, False, True), 2, plan.Cgi, device=dev)
+            f_b = lambda: C.conv_fwd_bn(gys, wd, dxs, part_d, dims_d, bdy, bdx, bn_y, coef, True)   # noqa: E731
+            t_b = timeit(f_b, a.iters)
         dwp = torch.empty(C.conv_wgrad_replicas(dims, dy, dx, False, False, bool(xc)) * plan.rows * plan.T * plan.Cip, device=dev)
         t_w = timeit(lambda: C.conv_wgrad(gys, [x], dwp, dims, dy, dx, False, xc, xr), a.iters)
         flops = 2.0 * n * oh * ow * co * ci * k[0] * k[1] * groups
         row = {'layer': name, 'fwd_ms': round(t_f, 4), 'dgrad_ms': round(t_d, 4), 'wgrad_ms': round(t_w, 4),
+               'dgrad_acc_ms': round(t_a, 4), 'dgrad_bn_ms': round(t_b, 4) if t_b is not None else None,
                'fwd_tflops': round(flops / t_f / 1e9, 1), 'dgrad_tflops': round(flops / t_d / 1e9, 1),
                'wgrad_tflops': round(flops / t_w / 1e9, 1)}
         if a.miopen:
@@ -148,11 +167,12 @@ def main():
         if sbuf is not None:
             row['stamps_fwd'] = stamp_summary(
                 C, sbuf, lambda: C.conv_fwd([x], wp, ys, None, part, dims, dy, dx, False, xc, xr))
-            row['stamps_dgrad'] = stamp_summary(
-                C, sbuf, lambda: C.conv_fwd(gys, wd, dxs, None, None, dims_d, bdy, bdx, s > 1))
-            for k in ('stamps_fwd', 'stamps_dgrad'):
+            row['stamps_dgrad'] = stamp_summary(C, sbuf, f_d)
+            row['stamps_dgrad_acc'] = stamp_summary(C, sbuf, f_a)
+            row['stamps_dgrad_bn'] = stamp_summary(C, sbuf, f_b) if f_b is not None else None
+            for k in ('stamps_fwd', 'stamps_dgrad', 'stamps_dgrad_acc', 'stamps_dgrad_bn'):
                 if row[k]:
-                    print(f"    {k[7:]:5s} fill {row[k]['fill_us']:6.2f} us  loop {row[k]['loop_us']:7.2f}  drain "
+                    print(f"    {k[7:]:9s} fill {row[k]['fill_us']:6.2f} us  loop {row[k]['loop_us']:7.2f}  drain "
                           f"{row[k]['drain_us']:6.2f}  fill+drain share {100 * row[k]['fill_drain_share']:5.1f} %  "
                           f"({row[k]['blocks']} blocks)", flush=True)
         row['halo_fwd'] = bool(C.conv_uses_halo(dims, dy, dx, False))
@@ -160,7 +180,8 @@ def main():
         res.append(row)
         tot['fwd'] += t_f; tot['dgrad'] += t_d; tot['wgrad'] += t_w
         print(f"{name:28s} fwd {t_f:7.3f} ms ({row['fwd_tflops']:6.1f} TF)  dgrad {t_d:7.3f} ({row['dgrad_tflops']:6.1f})"
-              f"  wgrad {t_w:7.3f} ({row['wgrad_tflops']:6.1f})" +
+              f"  wgrad {t_w:7.3f} ({row['wgrad_tflops']:6.1f})  dgrad+acc {t_a:7.3f}" +
+              (f"  dgrad+bn {t_b:7.3f}" if t_b is not None else '') +
               (f"  miopen-fwd {row['miopen_fwd_ms']:7.3f}" if a.miopen else ''), flush=True)
     print(json.dumps({'batch': a.batch, 'size': a.size, 'halo': a.halo, 'split': a.split, 'layers': res, 'totals_ms': tot}))
 
