@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "launchers.h"
+#include "wgrad_walk.h"
 
 namespace {
 
@@ -1706,6 +1707,33 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv_set_wgrad_gemm", [](int64_t mode) { conv_wgrad_gemm_set((int)mode); });
   m.def("conv_wgrad_gemm_force_cfg", [](int64_t c) { conv_wgrad_gemm_force_cfg((int)c); });
   m.def("conv_wgrad_gemm_num_cfgs", []() { return conv_wgrad_gemm_num_cfgs(); });
+  m.def("conv_wgrad_gemm_force_splits", [](int64_t n) { conv_wgrad_gemm_force_splits((int)n); });
+  m.def("conv_wgrad_gemm_set_ring", [](int64_t base, int64_t variant) { conv_wgrad_gemm_set_ring((int)base, (int)variant); });
+  m.def("conv_wgrad_gemm_cfg_info", [](int64_t cfg) {   // (wm, wn, fm, fn, NS, BP, base geometry)
+    int o[7];
+    conv_wgrad_gemm_cfg_info((int)cfg, o);
+    return std::vector<int64_t>(o, o + 7);
+  });
+  m.def("conv_wgrad_gemm_plan_cfg", [](std::vector<int64_t> dims, std::vector<int64_t> dy, std::vector<int64_t> dx, bool pro) {
+    return conv_wgrad_gemm_plan_cfg(make_geom(dims, dy, dx), pro);
+  });
+  // host trace of the weight-gradient GEMM's pixel cursor (wgrad_walk.h): dims = (N, IH, IW, OH, OW, stride), the
+  // walk starts at output pixel `row` and advances `step` pixels per stage; per stage (tap inside the batch and
+  // the image, input pixel index of tap (dy, dx))
+  m.def("wgrad_cursor_trace", [](std::vector<int64_t> dims, int64_t row, std::vector<int64_t> tap, int64_t step,
+                                 int64_t stages) {
+    TORCH_CHECK(dims.size() == 6 && tap.size() == 2 && step > 0 && row >= 0, "wgrad_cursor_trace: arguments");
+    const int N = (int)dims[0], IH = (int)dims[1], IW = (int)dims[2], OH = (int)dims[3], OW = (int)dims[4];
+    const WgWalk w = wg_walk_make(N, IH, IW, OH, OW, (int)dims[5], (int)step);
+    WgCursor c = wg_cursor_init(w, (int)(row / (OH * OW)), (int)((row % (OH * OW)) / OW), (int)(row % OW));
+    std::vector<std::pair<bool, int64_t>> out;
+    for (int64_t s = 0; s < stages; ++s) {
+      const bool in = wg_cursor_in(w, c, (int)tap[0], (int)tap[1]);
+      out.emplace_back(in, in ? (int64_t)(uint32_t)(c.base + (uint32_t)((int)tap[0] * IW + (int)tap[1])) : (int64_t)-1);
+      wg_cursor_advance(w, c);
+    }
+    return out;
+  });
   m.def("conv_uses_wgrad_gemm", [](std::vector<int64_t> dims, std::vector<int64_t> dy, std::vector<int64_t> dx, bool trans) {
     return conv_wgrad_gemm_ok(make_geom(dims, dy, dx), trans);
   });

@@ -79,6 +79,14 @@ void conv_wgrad_gemm_set(int mode);   // 0 off, 1 auto (planner), 2 every eligib
 int conv_wgrad_gemm_mode();
 void conv_wgrad_gemm_force_cfg(int cfg);
 int conv_wgrad_gemm_num_cfgs();
+// tests / A-B knobs: the number of pixel splits (-1: the planner's rule); the ring variant the planner maps a base
+// tile geometry to (variant < 0: the table's own); a configuration's (wm, wn, fm, fn, NS, BP, base geometry).
+// Both knobs are process-global and stay set until set back: a caller that changes them (the tests, tools/
+// conv_bench.py --wgrad-ring) resets them or ends the process.
+void conv_wgrad_gemm_force_splits(int n);
+void conv_wgrad_gemm_set_ring(int base, int variant);
+void conv_wgrad_gemm_cfg_info(int cfg, int out[7]);
+int conv_wgrad_gemm_plan_cfg(const ConvGeom& g, bool pro);
 
 // conv.hip
 int conv_pick_mi(int rows);

@@ -86,6 +86,9 @@ def main():
                     help='in-kernel clock stamps per block (needs a -DGK_STAMP side build loaded through MSP_C_SO): '
                     'median fill / main loop / drain per layer: forward, data-gradient, and the data-gradient '
                     'through the accumulate and the BN-backward epilogues')
+    ap.add_argument('--wgrad-only', action='store_true', help='time the weight gradients only (knock-out / ring sweeps)')
+    ap.add_argument('--wgrad-ring', default='', help="weight-gradient GEMM ring variants for this run, 'geometry:variant,...' "
+                    "(configuration indices of csrc/conv_wgrad_gemm.hip kWgCfgs; 'base': every geometry on its 2 x 64 ring)")
     ap.add_argument('--only', default='', help='substring filter on layer names')
     ap.add_argument('--levels', default='', help='comma list of levels to run (e.g. 3,4,5,6)')
     ap.add_argument('--prologue', action='store_true',
@@ -97,6 +100,14 @@ def main():
     C.conv_set_halo(bool(a.halo))
     C.conv_set_halo_split(a.split)
     C.conv_gemm_force_cfg(a.gemm_cfg)
+    if a.wgrad_ring == 'base':
+        for b in range(C.conv_wgrad_gemm_num_cfgs()):
+            if C.conv_wgrad_gemm_cfg_info(b)[6] == b:
+                C.conv_wgrad_gemm_set_ring(b, b)
+    elif a.wgrad_ring:
+        for pair in a.wgrad_ring.split(','):
+            b, v = (int(t) for t in pair.split(':'))
+            C.conv_wgrad_gemm_set_ring(b, v)
     sbuf = None
     if a.gemm_stamps:
         if not C.conv_gemm_stamp_buffer(None):
@@ -129,6 +140,19 @@ def main():
             st[0, :ci] = torch.rand(ci, device=dev) + 0.5
             st[1, :ci] = torch.randn(ci, device=dev) * 0.1
             xc, xr = [st], 1
+        if a.wgrad_only:
+            gys = [torch.randn_like(y, dtype=torch.float32).to(torch.bfloat16) for y in ys]
+            dwp = torch.empty(C.conv_wgrad_replicas(dims, dy, dx, False, False, bool(xc)) * plan.rows * plan.T * plan.Cip,
+                              device=dev)
+            t_w = timeit(lambda: C.conv_wgrad(gys, [x], dwp, dims, dy, dx, False, xc, xr), a.iters)
+            cfg = C.conv_wgrad_gemm_plan_cfg(dims, dy, dx, bool(xc)) if hasattr(C, 'conv_wgrad_gemm_plan_cfg') else -1
+            gemm = bool(C.conv_uses_wgrad_gemm(dims, dy, dx, False)) and not C.conv_wgrad_uses_halo(dims, dy, dx, False)
+            flops = 2.0 * n * oh * ow * co * ci * k[0] * k[1] * groups
+            res.append({'layer': name, 'wgrad_ms': round(t_w, 4), 'wgrad_tflops': round(flops / t_w / 1e9, 1),
+                        'wgrad_cfg': cfg if gemm else None})
+            tot['wgrad'] += t_w
+            print(f"{name:28s} wgrad {t_w:7.3f} ({flops / t_w / 1e9:6.1f})  cfg {cfg if gemm else '-'}", flush=True)
+            continue
         t_f = timeit(lambda: C.conv_fwd([x], wp, ys, None, part, dims, dy, dx, False, xc, xr), a.iters)
         wd, Kp_d = plan.pack_dgrad(dev)
         gys = [torch.randn_like(y, dtype=torch.float32).to(torch.bfloat16) for y in ys]
